@@ -103,3 +103,38 @@ def test_bench_single_rank_process_group_runs_dp_path():
     assert out["n_gpus"] == 1 and cfg["parallelism"] == "dp1" and out["dist_backend"] == "gloo"
     assert out["comm"] == "torch" and cfg["step"] == "eager-dp"
     assert out["value"] is not None and out["value"] > 0 and "error" not in out
+
+
+def test_bench_dump_outputs_is_reproducible(tmp_path):
+    """``--dump-outputs DIR`` on a plain one-rank run (CPU, RT-1-tiny, fp32): loss / params / grads of the last timed
+    step land as float32 ``.npy`` files, params and grads sampled at the same positions, and a second run with the
+    same arguments writes the same bytes (seeded weights and batches).  ``--steps`` sets the number of timed steps
+    issued.  A plain run makes no graph == eager comparison."""
+    import numpy as np
+    BASE1 = [a if a != "2" or i != 3 else "1" for i, a in enumerate(BASE)] + ["--dtype", "fp32"]
+    env = dict(os.environ, PYTHONPATH=ROOT, OMP_NUM_THREADS="2")
+    for k in ("RANK", "WORLD_SIZE", "RT1_PG_WORLD1"):
+        env.pop(k, None)
+
+    def run(name, extra=()):
+        d = tmp_path / name
+        r = subprocess.run(BASE1 + ["--dump-outputs", str(d)] + list(extra), env=env, capture_output=True, text=True,
+                           timeout=240)
+        assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        timed = [ln for ln in r.stderr.splitlines() if ln.startswith("[bench] step ")]
+        return json.loads(lines[0]), {n: np.load(d / f"{n}.npy") for n in ("loss", "params", "grads")}, len(timed)
+
+    out, a, timed = run("a", ["--steps", "3"])
+    assert out["steps"] == 3 and timed == 3 and out["warmup"] == 1
+    assert out["ms_per_step"] > 0 and out["config"]["graph_eq_eager"] is None
+    assert out["config"]["full"] is False and out["config"]["dumped_outputs"]["loss"] == [1]
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == ["grads.npy", "loss.npy", "params.npy"]
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert a["loss"].shape == (1,) and a["params"].shape == a["grads"].shape and a["params"].size > 1000
+    assert np.isfinite(a["loss"]).all() and np.abs(a["grads"]).max() > 0
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    _, b, _ = run("b", ["--steps", "3"])
+    for n in a:
+        assert a[n].tobytes() == b[n].tobytes(), n

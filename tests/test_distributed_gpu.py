@@ -65,7 +65,7 @@ def test_bench_two_ranks_gloo_rehearsal():
     graph step, and bit-identical parameters on both ranks after the timed steps."""
     env = dict(os.environ, PYTHONPATH=ROOT, RT1_DIST_BACKEND="gloo", MASTER_PORT="29549")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "2",
-           "--batch_per_gpu", "16"]
+           "--batch_per_gpu", "16", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -122,7 +122,7 @@ def test_native_comm_single_rank_engine_matches_graph_step():
 def _bench_gloo2(env_extra, port):
     env = dict(os.environ, PYTHONPATH=ROOT, RT1_DIST_BACKEND="gloo", MASTER_PORT=str(port), **env_extra)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "2",
-           "--batch_per_gpu", "8", "--height", "128", "--width", "128"]
+           "--batch_per_gpu", "8", "--height", "128", "--width", "128", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -190,7 +190,7 @@ def test_bench_single_rank_rccl_process_group_graph_dp():
     env.pop("RANK", None)
     env.pop("WORLD_SIZE", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
-           "--batch_per_gpu", "8", "--height", "128", "--width", "128", "--bucket_cap_mb", "8"]
+           "--batch_per_gpu", "8", "--height", "128", "--width", "128", "--bucket_cap_mb", "8", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
