@@ -56,6 +56,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--backend", choices=["auto", "hip", "torch"], default="auto")
     p.add_argument("--num_layers", type=int, default=8)
     p.add_argument("--weight_decay", type=float, default=0.0, help="AdamW decoupled decay (0 = Adam, reference)")
+    p.add_argument("--gradient_clip_val", type=float, default=0.0,
+                   help="clip the global gradient norm to this value on the device (Lightning's name; 0 = off)")
+    p.add_argument("--skip_nonfinite_steps", action="store_true",
+                   help="a step whose gradient norm is not finite changes nothing: no Adam update, BN running "
+                        "statistics rolled back")
     p.add_argument("--bucket_cap_mb", type=float, default=32.0)
     p.add_argument("--no_broadcast_buffers", action="store_true")
     p.add_argument("--comm", choices=["torch", "native"], default="torch",
@@ -200,7 +205,12 @@ def train(args):
     use_graph = args.graph in ("on", "auto")
     engine = TrainEngine(model, cfg, lr=args.lr, milestones=args.milestones, weight_decay=args.weight_decay,
                          bucket_cap_mb=args.bucket_cap_mb, broadcast_buffers=not args.no_broadcast_buffers,
-                         comm=args.comm, graph=use_graph)
+                         comm=args.comm, graph=use_graph,
+                         max_grad_norm=args.gradient_clip_val if args.gradient_clip_val > 0 else None,
+                         skip_nonfinite=args.skip_nonfinite_steps)
+    if ctx.is_main:
+        print(f"[train] gradient_clip_val {args.gradient_clip_val if args.gradient_clip_val > 0 else 'off'}, "
+              f"skip_nonfinite_steps {'on' if args.skip_nonfinite_steps else 'off'}", flush=True)
     ckpt = ModelCheckpoint(os.path.join(args.ckpt_dir, args.exp_name), every_n_epochs=args.ckpt_every_n_epochs)
     loggers = []
     if ctx.is_main:

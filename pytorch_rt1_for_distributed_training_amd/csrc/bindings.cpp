@@ -94,6 +94,72 @@ void flat_adam_dev(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v, at::T
                  "flat_adam_dev");
 }
 
+bool aligned16(const at::Tensor& t) { return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0; }
+
+void check_clip_state(const at::Tensor& cs, const char* what) {
+    check_dev(cs, "clip_state", at::kFloat);
+    TORCH_CHECK(cs.numel() >= 8 && aligned16(cs), what, ": clip_state must be fp32[8], 16-byte aligned");
+}
+
+// global-norm clipping / non-finite skip (csrc/kernels/gradnorm.hip): flat gradient -> fp64 partials -> clip_state
+int64_t gradnorm_partials(int64_t n) { return rt1_gradnorm_partials(n); }
+
+void grad_sumsq(at::Tensor g, at::Tensor partials) {
+    check_dev(g, "grad", at::kFloat);
+    check_dev(partials, "partials", at::kDouble);
+    const int64_t n = g.numel();
+    TORCH_CHECK(n > 0 && partials.numel() >= rt1_gradnorm_partials(n), "grad_sumsq: need ", rt1_gradnorm_partials(n),
+                " partials for ", n, " elements");
+    TORCH_CHECK(g.device() == partials.device(), "grad_sumsq: tensors on different devices");
+    TORCH_CHECK(aligned16(g), "grad_sumsq: the gradient must be 16-byte aligned");
+    check_launch(rt1_grad_sumsq(g.data_ptr<float>(), n, partials.data_ptr<double>(), cur_stream()), "grad_sumsq");
+}
+
+void grad_clip_finalize(at::Tensor partials, int64_t P, double max_norm, double grad_scale, bool skip_nonfinite,
+                        at::Tensor clip_state) {
+    check_dev(partials, "partials", at::kDouble);
+    check_clip_state(clip_state, "grad_clip_finalize");
+    TORCH_CHECK(P >= 1 && P <= partials.numel(), "grad_clip_finalize: P out of range");
+    TORCH_CHECK(clip_state.device() == partials.device(), "grad_clip_finalize: tensors on different devices");
+    check_launch(rt1_grad_clip_finalize(partials.data_ptr<double>(), (int)P, (float)max_norm, (float)grad_scale,
+                                        skip_nonfinite ? 1 : 0, clip_state.data_ptr<float>(), cur_stream()),
+                 "grad_clip_finalize");
+}
+
+void buffer_guard_(at::Tensor buf, at::Tensor shadow, at::Tensor clip_state) {
+    check_dev(buf, "buf", at::kFloat);
+    check_dev(shadow, "shadow", at::kFloat);
+    check_clip_state(clip_state, "buffer_guard_");
+    const int64_t n = buf.numel();
+    TORCH_CHECK(n > 0 && shadow.numel() == n, "buffer_guard_: size mismatch");
+    TORCH_CHECK(buf.device() == shadow.device() && buf.device() == clip_state.device(),
+                "buffer_guard_: tensors on different devices");
+    TORCH_CHECK(aligned16(buf) && aligned16(shadow), "buffer_guard_: buffers must be 16-byte aligned");
+    TORCH_CHECK(buf.data_ptr() != shadow.data_ptr(), "buffer_guard_: buf and shadow must be distinct");
+    check_launch(rt1_buffer_guard(buf.data_ptr<float>(), shadow.data_ptr<float>(), n, clip_state.data_ptr<float>(),
+                                  cur_stream()), "buffer_guard_");
+}
+
+void flat_adam_clip_dev(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v, at::Tensor state,
+                        at::Tensor clip_state, double beta1, double beta2, double eps, double weight_decay,
+                        double grad_scale) {
+    check_dev(p, "param", at::kFloat);
+    check_dev(g, "grad", at::kFloat);
+    check_dev(m, "exp_avg", at::kFloat);
+    check_dev(v, "exp_avg_sq", at::kFloat);
+    check_dev(state, "state", at::kFloat);
+    check_clip_state(clip_state, "flat_adam_clip_dev");
+    const int64_t n = p.numel();
+    TORCH_CHECK(g.numel() == n && m.numel() == n && v.numel() == n && state.numel() >= 2, "flat_adam_clip_dev: sizes");
+    TORCH_CHECK(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v),
+                "flat_adam_clip_dev: buffers must be 16-byte aligned");
+    check_launch(rt1_flat_adam_clip_dev(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(),
+                                        v.data_ptr<float>(), n, state.data_ptr<float>(), clip_state.data_ptr<float>(),
+                                        (float)beta1, (float)beta2, (float)eps, (float)weight_decay, (float)grad_scale,
+                                        cur_stream()),
+                 "flat_adam_clip_dev");
+}
+
 // Deterministic fixed-order sum over the rows of B x [R, C] (fp32 or bf16, contiguous) -> B x [C] fp32
 // (csrc/kernels/reduce.hip).  Replaces ATen's tall-reduction path, whose cross-workgroup semaphore combine gave
 // wrong weight gradients under hipGraph replay.
@@ -1366,6 +1432,11 @@ PYBIND11_MODULE(_rt1_hip, m) {
     m.doc() = "RT-1 HIP/CDNA4 kernels (gfx950)";
     m.def("flat_adam", &flat_adam, "fused Adam/AdamW over flat fp32 buffers");
     m.def("flat_adam_dev", &flat_adam_dev, "fused Adam/AdamW, step/lr read from a device tensor (graph-replayable)");
+    m.def("flat_adam_clip_dev", &flat_adam_clip_dev, "flat_adam_dev obeying clip_state (clip coefficient, skipped step)");
+    m.def("gradnorm_partials", &gradnorm_partials, "fp64 partial sums grad_sumsq writes for n floats");
+    m.def("grad_sumsq", &grad_sumsq, "deterministic sum of squares of a flat fp32 gradient -> fp64 partials");
+    m.def("grad_clip_finalize", &grad_clip_finalize, "partials -> clip_state {norm, coef, ok, counters}");
+    m.def("buffer_guard_", &buffer_guard_, "ok ? shadow = buf : buf = shadow");
     m.def("bn_stats", &bn_stats);
     m.def("bn_finalize", &bn_finalize);
     m.def("xgram", &xgram);

@@ -62,7 +62,60 @@ __global__ __launch_bounds__(256) void flat_adam_kernel(float* __restrict__ p, c
     }
 }
 
+// The same update under the verdict of gradnorm.hip's clip_state {norm, coef, ok, skipped, ...}: a skipped step
+// (ok == 0) touches nothing -- every workgroup leaves before its first load, the branch is uniform -- and does not
+// advance the bias correction (t = step - skipped steps, as a skipped optimizer.step() under torch's GradScaler);
+// otherwise g = (g * grad_scale) * coef, which with coef == 1 is bit for bit the update of flat_adam_kernel.
+__global__ __launch_bounds__(256) void flat_adam_clip_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                             float* __restrict__ m, float* __restrict__ v,
+                                                             int64_t n4, int64_t n, AdamArgs a,
+                                                             const float* __restrict__ state,
+                                                             const float* __restrict__ clip_state) {
+    if (clip_state[2] == 0.f) return;
+    const float gs = a.grad_scale;
+    a.grad_scale = clip_state[1];      // adam_elem's own multiply applies the clip coefficient second
+    {
+        const float t = state[0] - clip_state[3], lr = state[1];
+        a.lr = lr;
+        a.step_size = lr / -expm1f(t * logf(a.beta1));
+        a.inv_sqrt_bc2 = rsqrtf(-expm1f(t * logf(a.beta2)));
+    }
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    float4* p4 = reinterpret_cast<float4*>(p);
+    const float4* g4 = reinterpret_cast<const float4*>(g);
+    float4* m4 = reinterpret_cast<float4*>(m);
+    float4* v4 = reinterpret_cast<float4*>(v);
+    for (; i < n4; i += stride) {
+        float4 pp = p4[i], gg = g4[i], mm = m4[i], vv = v4[i];
+        adam_elem(pp.x, gg.x * gs, mm.x, vv.x, a);
+        adam_elem(pp.y, gg.y * gs, mm.y, vv.y, a);
+        adam_elem(pp.z, gg.z * gs, mm.z, vv.z, a);
+        adam_elem(pp.w, gg.w * gs, mm.w, vv.w, a);
+        p4[i] = pp; m4[i] = mm; v4[i] = vv;
+    }
+    for (int64_t j = n4 * 4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += stride) {
+        float pp = p[j], mm = m[j], vv = v[j];
+        adam_elem(pp, g[j] * gs, mm, vv, a);
+        p[j] = pp; m[j] = mm; v[j] = vv;
+    }
+}
+
 }  // namespace
+
+extern "C" int rt1_flat_adam_clip_dev(float* p, const float* g, float* m, float* v, int64_t n, const float* state,
+                                      const float* clip_state, float beta1, float beta2, float eps,
+                                      float weight_decay, float grad_scale, hipStream_t stream) {
+    if (state == nullptr || clip_state == nullptr) return (int)hipErrorInvalidValue;
+    AdamArgs a{0.f, beta1, beta2, eps, weight_decay, 0.f, 1.f, grad_scale};
+    const int64_t n4 = n / 4;
+    int64_t blocks = (n4 + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    if (blocks < 1) blocks = 1;
+    hipLaunchKernelGGL(flat_adam_clip_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, p, g, m, v, n4, n, a,
+                       state, clip_state);
+    return (int)hipGetLastError();
+}
 
 extern "C" int rt1_flat_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1,
                              float beta2, float eps, float weight_decay, float step_size, float inv_sqrt_bc2,

@@ -13,6 +13,21 @@ int rt1_flat_adam(float* p, const float* g, float* m, float* v, int64_t n, float
 // graph-replayable variant: state = {step, lr} on the device (the step is advanced by the caller's device op)
 int rt1_flat_adam_dev(float* p, const float* g, float* m, float* v, int64_t n, const float* state, float beta1,
                       float beta2, float eps, float weight_decay, float grad_scale, hipStream_t stream);
+// rt1_flat_adam_dev under gradnorm.hip's clip_state: nothing is touched when ok == 0, g = (g * grad_scale) * coef
+// otherwise, Adam step = state[0] - skipped steps
+int rt1_flat_adam_clip_dev(float* p, const float* g, float* m, float* v, int64_t n, const float* state,
+                           const float* clip_state, float beta1, float beta2, float eps, float weight_decay,
+                           float grad_scale, hipStream_t stream);
+
+// gradnorm.hip (deterministic global gradient norm -> clip_state fp32[8] = {norm, coef, ok, skipped steps, clipped
+// steps, consecutive skipped steps, 0, 0}; rt1_gradnorm_partials: workgroups / fp64 partials for n floats, a function
+// of n alone, 0 for n <= 0)
+int rt1_gradnorm_partials(int64_t n);
+int rt1_grad_sumsq(const float* g, int64_t n, double* partials, hipStream_t stream);
+int rt1_grad_clip_finalize(const double* partials, int P, float max_norm, float grad_scale, int skip_nonfinite,
+                           float* clip_state, hipStream_t stream);
+// ok ? shadow = buf : buf = shadow
+int rt1_buffer_guard(float* buf, float* shadow, int64_t n, const float* clip_state, hipStream_t stream);
 
 }  // extern "C"
 

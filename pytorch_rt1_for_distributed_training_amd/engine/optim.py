@@ -27,7 +27,8 @@ from ..parallel.flat import FlatParameters
 class FlatAdam(torch.optim.Optimizer):
     def __init__(self, flat: FlatParameters, lr: float = 5e-4, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.0, all_params: Optional[Sequence[torch.nn.Parameter]] = None,
-                 use_kernel: Optional[bool] = None):
+                 use_kernel: Optional[bool] = None, max_grad_norm: Optional[float] = None,
+                 skip_nonfinite: bool = False):
         self.flat = flat
         params = list(all_params) if all_params is not None else list(flat.params)
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False,
@@ -46,6 +47,18 @@ class FlatAdam(torch.optim.Optimizer):
         if use_kernel:
             from ..ops import adam as adam_ops
             self._kernel = adam_ops
+        # global-norm clipping / non-finite step skip, decided on the device (ops.adam.grad_norm_clip_): clip_state is
+        # fp32[8] = {norm, coef, ok, skipped steps, clipped steps, consecutive skipped steps, 0, 0} on every backend
+        self.max_grad_norm = float(max_grad_norm) if max_grad_norm is not None and max_grad_norm > 0 else 0.0
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.clip_enabled = self.max_grad_norm > 0.0 or self.skip_nonfinite
+        self.clip_state = None
+        self._partials = None
+        if self.clip_enabled:
+            self.clip_state = torch.zeros(8, dtype=torch.float32, device=flat.data.device)
+            if self._kernel is not None:
+                self._partials = torch.zeros(self._kernel.gradnorm_partials(flat.grad.numel()), dtype=torch.float64,
+                                             device=flat.data.device)
 
     @torch.no_grad()
     def step(self, closure=None, grad_scale: float = 1.0):
@@ -63,6 +76,14 @@ class FlatAdam(torch.optim.Optimizer):
                 self.write_device_state(t - 1, lr)
             self.dev_state[0:1].add_(1.0)
             self._dev_step = t
+            if self.clip_enabled:
+                self._kernel.grad_norm_clip_(self.flat.grad, self.clip_state, self._partials,
+                                             max_norm=self.max_grad_norm, grad_scale=grad_scale,
+                                             skip_nonfinite=self.skip_nonfinite)
+                self._kernel.flat_adam_clip_dev_step(self.flat.data, self.flat.grad, self.exp_avg, self.exp_avg_sq,
+                                                     self.dev_state, self.clip_state, beta1=b1, beta2=b2, eps=eps,
+                                                     weight_decay=wd, grad_scale=grad_scale)
+                return loss
             self._kernel.flat_adam_dev_step(self.flat.data, self.flat.grad, self.exp_avg, self.exp_avg_sq,
                                             self.dev_state, beta1=b1, beta2=b2, eps=eps, weight_decay=wd,
                                             grad_scale=grad_scale)
@@ -70,6 +91,14 @@ class FlatAdam(torch.optim.Optimizer):
         grad = self.flat.grad
         if grad_scale != 1.0:
             grad = grad * grad_scale
+        if self.clip_enabled:
+            # torch fallback of the clip kernels: same semantics, same clip_state layout (host reads are fine here)
+            coef, ok = self._clip_verdict(grad)
+            if not ok:
+                return loss
+            if coef != 1.0:
+                grad = grad * coef
+            t -= self.skipped_steps
         p = self.flat.data
         if wd:
             p.mul_(1.0 - lr * wd)
@@ -80,6 +109,33 @@ class FlatAdam(torch.optim.Optimizer):
         denom = (self.exp_avg_sq.sqrt() / math.sqrt(bc2)).add_(eps)
         p.addcdiv_(self.exp_avg, denom, value=-lr / bc1)
         return loss
+
+    def _clip_verdict(self, grad: torch.Tensor):
+        """CPU / no-kernel path: norm of the (already averaged) gradient -> clip_state, returns (coef, ok)."""
+        norm = float(grad.double().pow(2).sum().sqrt())
+        finite = math.isfinite(norm)
+        coef = 1.0
+        if self.max_grad_norm > 0.0 and finite:
+            coef = min(1.0, self.max_grad_norm / (norm + 1e-6))
+        ok = not (self.skip_nonfinite and not finite)
+        cs = self.clip_state.tolist()
+        self.clip_state.copy_(torch.tensor([norm, coef, float(ok), cs[3] + (0.0 if ok else 1.0),
+                                            cs[4] + (1.0 if ok and coef < 1.0 else 0.0),
+                                            0.0 if ok else cs[5] + 1.0, 0.0, 0.0], dtype=torch.float32))
+        return coef, ok
+
+    @property
+    def last_grad_norm(self) -> Optional[torch.Tensor]:
+        """Norm of the last step's data-parallel mean gradient before clipping: a 0-d device view, no sync."""
+        return self.clip_state[0] if self.clip_state is not None else None
+
+    @property
+    def skipped_steps(self) -> int:
+        return int(self.clip_state[3]) if self.clip_state is not None else 0
+
+    @property
+    def clipped_steps(self) -> int:
+        return int(self.clip_state[4]) if self.clip_state is not None else 0
 
     def write_device_state(self, step: int, lr: float):
         """Host -> device write of {step, lr} (a small H2D copy; outside any capture)."""
@@ -106,10 +162,12 @@ class FlatAdam(torch.optim.Optimizer):
             d["params"] = ids
             groups.append(d)
         state = {}
+        # skipped steps never reached the moments: the checkpoint carries the effective Adam step
+        step = self.step_count - self.skipped_steps
         if self.step_count > 0:
             for p, o in zip(self.flat.params, self.flat.offsets):
                 n = p.numel()
-                state[index[id(p)]] = {"step": torch.tensor(float(self.step_count)),
+                state[index[id(p)]] = {"step": torch.tensor(float(step)),
                                        "exp_avg": self.exp_avg[o:o + n].view_as(p).detach().clone(),
                                        "exp_avg_sq": self.exp_avg_sq[o:o + n].view_as(p).detach().clone()}
         return {"state": state, "param_groups": groups}
@@ -135,6 +193,9 @@ class FlatAdam(torch.optim.Optimizer):
                 self.exp_avg_sq[o:o + n].copy_(st["exp_avg_sq"].reshape(-1))
                 steps.append(int(float(st["step"])))
         self.step_count = max(steps) if steps else 0
+        if self.clip_state is not None:
+            self.clip_state.zero_()      # the host counter is the effective step again
+            self._dev_step = None
 
 
 def multistep_lr(optimizer: torch.optim.Optimizer, milestones: List[int], gamma: float = 0.1):

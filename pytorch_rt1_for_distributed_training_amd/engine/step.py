@@ -23,6 +23,12 @@ each gradient bucket completes (``engine.graphs.SegmentedCapture``); a step repl
 RCCL all-reduce on the comm stream, replays segment i+1 while that all-reduce runs, ... then one fused Adam
 launch.  Collectives are never captured; they overlap the backward exactly where DDP's hooks would fire them.
 
+``max_grad_norm`` / ``skip_nonfinite`` (both off by default, and then nothing here changes): the optimizer takes the
+global norm of the all-reduced flat gradient on the device (``csrc/kernels/gradnorm.hip``), the clip variant of the
+fused Adam scales the gradient or leaves a non-finite step untouched, and ``buffer_guard_`` rolls the BN running
+statistics of such a step back -- all inside the captured graph, with no host read.  The norm's summation order
+depends only on the buffer length, so every rank takes the same decision without another collective.
+
 No ``network_state`` is fabricated (the reference samples a random one on the
 CPU and copies it to the GPU every step only to read its shape).
 """
@@ -108,7 +114,7 @@ class TrainEngine:
                  gamma: float = 0.1, weight_decay: float = 0.0, bucket_cap_mb: float = 32.0,
                  broadcast_buffers: bool = True, device: Optional[torch.device] = None,
                  grad_comm_dtype: torch.dtype = torch.float32, order_probe: bool = True, comm: str = "torch",
-                 graph: bool = False):
+                 graph: bool = False, max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False):
         ctx = pdist.context()
         self.cfg = cfg
         self.device = device or pdist.default_device()
@@ -146,7 +152,18 @@ class TrainEngine:
         self.ddp = DataParallel(self.model, self.flat, bucket_cap_mb=bucket_cap_mb,
                                 broadcast_buffers=broadcast_buffers, grad_comm_dtype=grad_comm_dtype, comm=native)
         self.optimizer = FlatAdam(self.flat, lr=lr, weight_decay=weight_decay,
-                                  all_params=list(self.model.parameters()))
+                                  all_params=list(self.model.parameters()), max_grad_norm=max_grad_norm,
+                                  skip_nonfinite=skip_nonfinite)
+        # skip_nonfinite: the forward of a bad batch has already written the BN running statistics when the norm
+        # kernel notices, so they live in one flat buffer (the data-parallel one when there is one) with a shadow copy
+        # of the last good state; buffer_guard_ advances or rolls back right after the optimizer step
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self._bn_flat = self._bn_shadow = None
+        if self.skip_nonfinite:
+            from ..parallel.flat import flatten_buffers
+            self._bn_flat = self.ddp.buffers if self.ddp.buffers is not None else flatten_buffers(self.model)
+            if self._bn_flat is not None:
+                self._bn_shadow = self._bn_flat.clone()
         self.scheduler = multistep_lr(self.optimizer, list(milestones), gamma)
         self.global_step = 0
         # one GPU: the whole step is one graph; data parallel: forward+backward is the graph, the gradient
@@ -189,6 +206,23 @@ class TrainEngine:
         order_idx = pdist.broadcast_object(order_idx)
         return [trainable[i] for i in order_idx]
 
+    def refresh_buffer_shadow(self):
+        """The BN running statistics were replaced from outside the step (checkpoint load, parameter broadcast):
+        they are the good state now."""
+        if self._bn_shadow is not None:
+            self._bn_shadow.copy_(self._bn_flat)
+
+    def _guard_buffers(self):
+        if self._bn_shadow is None:
+            return
+        opt = self.optimizer
+        if opt._kernel is not None:
+            opt._kernel.buffer_guard_(self._bn_flat, self._bn_shadow, opt.clip_state)
+        elif float(opt.clip_state[2]) != 0.0:
+            self._bn_shadow.copy_(self._bn_flat)
+        else:
+            self._bn_flat.copy_(self._bn_shadow)
+
     def autocast(self):
         if self.compute_dtype == torch.float32 or self.backend == "hip":
             return contextlib.nullcontext()
@@ -210,6 +244,7 @@ class TrainEngine:
             loss.backward()
         self.ddp.finish()
         self.optimizer.step(grad_scale=self.ddp.grad_scale)
+        self._guard_buffers()
         return loss.detach()
 
     def train_step(self, batch: Dict) -> torch.Tensor:
@@ -336,6 +371,7 @@ class TrainEngine:
         else:
             self.ddp.wait_all(works)
         self.optimizer.step(grad_scale=self.ddp.grad_scale)
+        self._guard_buffers()
         self.global_step += 1
         return self._static_loss.clone()
 
@@ -403,7 +439,9 @@ class TrainEngine:
                         bufs=[b.detach().clone() for b in self.model.buffers()],
                         rng=(torch.cuda.get_rng_state(self.device) if self.device.type == "cuda" else None),
                         cpu_rng=torch.get_rng_state(),
-                        ctr={d: t.clone() for d, t in _rng._COUNTERS.items()}, gstep=self.global_step)
+                        ctr={d: t.clone() for d, t in _rng._COUNTERS.items()}, gstep=self.global_step,
+                        clip=(opt.clip_state.clone() if opt.clip_state is not None else None),
+                        shadow=(self._bn_shadow.clone() if self._bn_shadow is not None else None))
 
     def _restore(self, s: Dict):
         from ..ops import rng as _rng
@@ -417,6 +455,10 @@ class TrainEngine:
                 b.copy_(c)
             for d, t in s["ctr"].items():
                 _rng._COUNTERS[d].copy_(t)
+            if s["clip"] is not None:
+                opt.clip_state.copy_(s["clip"])
+            if s["shadow"] is not None:
+                self._bn_shadow.copy_(s["shadow"])
         opt.step_count, opt._dev_step, opt._dev_lr = s["step"], s["dev_step"], s["dev_lr"]
         if s["rng"] is not None:
             torch.cuda.set_rng_state(s["rng"], self.device)

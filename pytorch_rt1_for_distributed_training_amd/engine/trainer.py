@@ -13,7 +13,12 @@ Differences: losses are accumulated on device and reduced across ranks only at
 log points (the reference's ``sync_dist=True`` all-reduces a scalar every
 step); ``eval_loss`` / ``test_loss`` are averaged over all ranks instead of
 reporting rank 0's shard; a non-finite training loss aborts the run with the
-step number (failure detection; the reference has none).
+step number (failure detection; the reference has none).  With the engine's
+``skip_nonfinite`` a step with a non-finite gradient is skipped on the device
+instead: the loss means are taken over the finite steps, ``grad_norm`` /
+``clipped_steps`` / ``skipped_steps`` are logged at each log interval, and the
+run aborts only when a whole log window (at least ``MIN_SKIPS_TO_ABORT``
+consecutive steps) was skipped.
 """
 from __future__ import annotations
 
@@ -33,6 +38,11 @@ from .step import TrainEngine
 
 class NonFiniteLoss(RuntimeError):
     pass
+
+
+# skip_nonfinite: consecutive skipped steps below which a log window made only of skipped steps is not yet fatal.  With
+# log_every_n_steps=1 every skipped step is such a window, and surviving one bad batch is what the option is for.
+MIN_SKIPS_TO_ABORT = 2
 
 
 class Trainer:
@@ -115,6 +125,7 @@ class Trainer:
         self.current_epoch = int(ck.get("epoch", -1)) + 1
         if self.engine.ddp.enabled:
             self.engine.ddp.broadcast_parameters()
+        self.engine.refresh_buffer_shadow()
 
     def validate(self, loader, limit=None, name="eval_loss") -> float:
         total, n = None, 0
@@ -160,29 +171,54 @@ class Trainer:
             self._log({"lr-Adam": e.lr})
             total, n, window, wn = None, 0, None, 0
             samples = 0
+            opt = e.optimizer
+            clip_on = bool(getattr(opt, "clip_enabled", False))
+            skip_on = bool(getattr(opt, "skip_nonfinite", False))
+            # skip_nonfinite: means over the finite-loss steps only (device-side masked sums and counts, no sync)
+            tcount = wcount = None
             t0 = time.perf_counter()
             for batch in self._iter(train_loader, self.limit_train):
                 loss = e.train_step(batch)
                 if e.graph and not self.graph_checked and (e._graph is not None or e._segments is not None):
                     self._check_graph(batch)
+                if skip_on:
+                    fin = torch.isfinite(loss)
+                    one = fin.to(torch.float32)
+                    loss = torch.where(fin, loss, torch.zeros_like(loss))
+                    tcount = one if tcount is None else tcount + one
+                    wcount = one if wcount is None else wcount + one
                 total = loss if total is None else total + loss
                 window = loss if window is None else window + loss
                 n += 1
                 wn += 1
                 samples += int(batch["action_label"]["action"].shape[0]) * pdist.context().world_size
                 if e.global_step % self.log_every == 0:
-                    step_loss = self._mean_across(window, wn)
-                    if not math.isfinite(step_loss):
+                    step_loss = self._mean_across(window, wcount if skip_on else wn)
+                    if skip_on:
+                        # a skipped step is survived, a dead run is not: every step of this window skipped
+                        # (MIN_SKIPS_TO_ABORT: a one-step window cannot tell the two apart)
+                        streak = int(opt.clip_state[5])
+                        if streak >= max(wn, MIN_SKIPS_TO_ABORT):
+                            raise NonFiniteLoss(f"{streak} consecutive non-finite steps skipped up to step "
+                                                f"{e.global_step}")
+                    elif not math.isfinite(step_loss):
                         raise NonFiniteLoss(f"non-finite train loss at step {e.global_step}: {step_loss}")
-                    self._log({"train_loss_step": step_loss})
-                    window, wn = None, 0
+                    metrics = {"train_loss_step": step_loss} if math.isfinite(step_loss) else {}
+                    if clip_on:
+                        metrics.update(grad_norm=float(opt.last_grad_norm), clipped_steps=opt.clipped_steps,
+                                       skipped_steps=opt.skipped_steps)
+                    self._log(metrics)
+                    window, wn, wcount = None, 0, None
                     if self.verbose:
-                        print(f"epoch {epoch} step {e.global_step} train_loss {step_loss:.6f} lr {e.lr:.2e}",
+                        extra = (f" grad_norm {metrics['grad_norm']:.4g} clipped {metrics['clipped_steps']} "
+                                 f"skipped {metrics['skipped_steps']}") if clip_on else ""
+                        print(f"epoch {epoch} step {e.global_step} train_loss {step_loss:.6f} lr {e.lr:.2e}{extra}",
                               flush=True)
             if e.device.type == "cuda":
                 torch.cuda.synchronize()
             dt = time.perf_counter() - t0
-            metrics = {"train_loss_epoch": self._mean_across(total, n) if total is not None else float("nan"),
+            metrics = {"train_loss_epoch": (self._mean_across(total, tcount if skip_on else n) if total is not None
+                                            else float("nan")),
                        "samples_per_sec": samples / dt if dt > 0 else 0.0}
             io = dict(getattr(getattr(self, "prefetcher", None), "stats", {}) or {})
             if io and n:

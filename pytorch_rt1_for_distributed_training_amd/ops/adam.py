@@ -21,6 +21,47 @@ def flat_adam_dev_step(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: tor
     load().flat_adam_dev(p, g, m, v, state, beta1, beta2, eps, weight_decay, grad_scale)
 
 
+CLIP_STATE_SLOTS = 8   # {norm, coef, ok, skipped steps, clipped steps, consecutive skipped steps, 0, 0}
+
+
+def gradnorm_partials(n: int) -> int:
+    """Number of fp64 partial sums ``grad_norm_clip_`` needs for a gradient of ``n`` floats (a function of n alone)."""
+    return int(load().gradnorm_partials(int(n)))
+
+
+def grad_norm_clip_(grad: torch.Tensor, clip_state: torch.Tensor, partials: torch.Tensor, *, max_norm: float,
+                    grad_scale: float = 1.0, skip_nonfinite: bool = False):
+    """Global norm of ``grad * grad_scale`` in a fixed summation order (``csrc/kernels/gradnorm.hip``, two launches,
+    no host read) -> ``clip_state`` fp32[8]: norm, clip coefficient (``max_norm <= 0``: always 1), ok (0 when
+    ``skip_nonfinite`` and the norm is not finite) and the cumulative skipped / clipped / consecutive-skipped
+    counters.  ``partials`` is an fp64 workspace of at least ``gradnorm_partials(grad.numel())`` elements."""
+    ext = load()
+    ext.grad_sumsq(grad, partials)
+    ext.grad_clip_finalize(partials, ext.gradnorm_partials(grad.numel()), float(max_norm), float(grad_scale),
+                           bool(skip_nonfinite), clip_state)
+
+
+def flat_adam_clip_dev_step(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, state: torch.Tensor,
+                            clip_state: torch.Tensor, *, beta1: float, beta2: float, eps: float, weight_decay: float,
+                            grad_scale: float = 1.0):
+    """``flat_adam_dev_step`` under ``clip_state``: untouched buffers when ok == 0, ``g = (g * grad_scale) * coef``
+    otherwise, and the Adam step is ``state[0]`` minus the skipped steps."""
+    load().flat_adam_clip_dev(p, g, m, v, state, clip_state, beta1, beta2, eps, weight_decay, grad_scale)
+
+
+def buffer_guard_(buf: torch.Tensor, shadow: torch.Tensor, clip_state: torch.Tensor):
+    """ok ? ``shadow = buf`` : ``buf = shadow`` (one launch): rolls back what a skipped step's forward wrote."""
+    load().buffer_guard_(buf, shadow, clip_state)
+
+
+def reference_clip_coef(g: torch.Tensor, max_norm: float, grad_scale: float = 1.0) -> float:
+    """fp64 oracle of the clip coefficient (``torch.nn.utils.clip_grad_norm_``'s formula) for ``g * grad_scale``."""
+    norm = float(g.double().pow(2).sum().sqrt()) * float(grad_scale)
+    if max_norm is None or max_norm <= 0 or not math.isfinite(norm):
+        return 1.0
+    return min(1.0, float(max_norm) / (norm + 1e-6))
+
+
 def reference_adam_step(p, g, m, v, *, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0):
     """Plain PyTorch fp32 oracle (same math as torch.optim.Adam / AdamW)."""
     g = g * grad_scale

@@ -6,7 +6,7 @@ OUT="$ROOT/build/asan"
 mkdir -p "$OUT"
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 SAN="-Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined -Xarch_host -fno-omit-frame-pointer"
-SRCS="dwconv pwgemm pwtall pwbwd block stem head tokenlearner transformer"
+SRCS="dwconv pwgemm pwtall pwbwd block stem head tokenlearner transformer gradnorm adam"
 pids=()
 for s in $SRCS; do
   src="$ROOT/pytorch_rt1_for_distributed_training_amd/csrc/kernels/$s.hip"

@@ -87,6 +87,33 @@ int main() {
     for (int p : {1, 64, 100, 120, 225, 256, 257, 1000}) rt1_tl_supported(p, 512, 64, 8);
     EXPECT(!rt1_tl_supported(257, 512, 64, 8));
     for (int v : {2, 128, 256, 512, 1024, 4096}) rt1_head_ce_supported(v, 512);
+    // gradient-norm grid: 1 <= P <= cap for every n >= 1 (no overflow in the grid arithmetic), 0 for n <= 0
+    {
+        const int cap = 2048;
+        for (int64_t n : {(int64_t)0, (int64_t)-1, (int64_t)-(1LL << 40), INT64_MIN}) EXPECT(rt1_gradnorm_partials(n) == 0);
+        int64_t sizes[48] = {1, 3, 63, 64, 65, 35233152, (1LL << 31) + 5, INT64_MAX};
+        int cnt = 8;
+        for (int b = 0; b <= 31; ++b) sizes[cnt++] = 1LL << b;
+        int prev = 0;
+        for (int k = 0; k < cnt; ++k) {
+            const int P = rt1_gradnorm_partials(sizes[k]);
+            EXPECT(P >= 1 && P <= cap);
+            ++checked;
+        }
+        for (int b = 0; b <= 31; ++b) {     // monotone in n
+            const int P = rt1_gradnorm_partials(1LL << b);
+            EXPECT(P >= prev);
+            prev = P;
+        }
+        EXPECT(rt1_gradnorm_partials(35233152) == cap);
+        // null pointers and empty buffers are rejected before any launch
+        EXPECT(rt1_grad_sumsq(nullptr, 64, nullptr, nullptr) != 0);
+        EXPECT(rt1_grad_clip_finalize(nullptr, 0, 1.f, 1.f, 1, nullptr, nullptr) != 0);
+        EXPECT(rt1_grad_clip_finalize(nullptr, cap + 1, 1.f, 1.f, 1, nullptr, nullptr) != 0);
+        EXPECT(rt1_buffer_guard(nullptr, nullptr, 0, nullptr, nullptr) != 0);
+        EXPECT(rt1_flat_adam_clip_dev(nullptr, nullptr, nullptr, nullptr, 64, nullptr, nullptr, 0.9f, 0.999f, 1e-8f,
+                                      0.f, 1.f, nullptr) != 0);
+    }
     std::printf("host checks: %ld shape cases, %d failures\n", checked, failures);
     return failures == 0 ? 0 : 1;
 }
