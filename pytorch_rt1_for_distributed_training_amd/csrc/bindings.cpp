@@ -971,6 +971,8 @@ at::Tensor block_tail(at::Tensor y3, at::Tensor scale, at::Tensor shift, OptT ke
     TORCH_CHECK(y3.dim() == 3, "y3 must be [N, HW, C]");
     const int N = (int)y3.size(0), HW = (int)y3.size(1), C = (int)y3.size(2);
     TORCH_CHECK(C % 8 == 0, "C % 8");
+    // wider rows miss the flat kernel (C <= 8192) and the row kernel writes only 2 x 256 vectors = 4096 channels of each
+    TORCH_CHECK(C <= 8192, "block_tail: C = ", C, " exceeds 8192 channels");
     check_f(scale, "scale", C); check_f(shift, "shift", C);
     check_opt_f(keep, "keep", N); check_opt_bf(skip, "skip", y3.numel());
     check_opt_f(fmul, "fmul", (int64_t)N * C); check_opt_f(fadd, "fadd", (int64_t)N * C);

@@ -593,6 +593,7 @@ int rt1_block_tail(const bf16_t* y3, int64_t M, int HW, int C, const float* scal
         return (int)hipGetLastError();
     }
     const int nv = C >> 3;
+    if (nv > 2 * BLOCK) return (int)hipErrorInvalidValue;   // the row kernel covers VPT = 2 vectors per lane: C <= 4096
     const int slots = nv <= BLOCK ? BLOCK / nv : 1;
     int64_t blocks = (M + slots - 1) / slots;
     if (blocks > 8192) blocks = 8192;
