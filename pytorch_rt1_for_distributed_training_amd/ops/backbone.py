@@ -2,33 +2,30 @@
 ``film_efficientnet/film_efficientnet_encoder.py:142-224``; ``models.efficientnet.MBConvBlock`` is the eager oracle).
 
 Activations are channels-last bf16 ``[N, H, W, C]`` (N = b*t frames) end to end; BatchNorm statistics, running stats
-and every reduction are fp32/fp64 with a fixed summation order.  Per MBConv block, as it runs today:
+and every reduction are fp32/fp64 with a fixed summation order.  Per MBConv block:
 
-forward   y1 = x @ We^T + BN1 partials   expand 1x1: pwgemm.hip MFMA kernels with a BN-stat epilogue where they cover
-                                         the shape, else hipBLASLt + bn_stats (deep blocks); x-mode (block 2): y1 is
-                                         never formed -- BN1 stats come from x's Gram moments (xexpand.hip)
-          y2 = dwconv(silu(bn1(y1)))    dw_fwd_kernel (dwconv.hip): BN1+SiLU prologue while staging the tile (x-mode:
-                                         y1 recomputed per tile on MFMA from x), BN2 partials epilogue
+forward   y1 = x @ We^T + BN1 constants  expand 1x1
+          y2 = dwconv(silu(bn1(y1)))    dw_fwd_kernel (dwconv.hip): BN1+SiLU prologue while staging the tile, BN2
+                                         partials epilogue
           s  = SE(mean_hw silu(bn2(y2))) frame_pool + fp32 fc1 / SiLU / fc2 / sigmoid
-          y3 = (silu(bn2(y2)) * s) @ Wp^T project 1x1 with the operand built in the GEMM's registers and a BN3-stat
-                                         epilogue: pwgemm.hip pw_gemm / pw_tall (blocks 0-17), gemm.hip (blocks 18-23); the two widest
-                                         project convs materialise A (bn_apply) for hipBLASLt
+          y3 = (silu(bn2(y2)) * s) @ Wp^T project 1x1 + BN3 constants
           out = (bn3(y3)*keep + x) * (1+gamma_film) + beta_film      block_tail
-backward  tail_bwd_reduce (FiLM grads + BN3 partials) -> bn_bwd_apply -> dA = dy3 @ Wp
-          proj_bwd (projbwd.hip): SE / BN2 backward sums and dWp from (dy3, y2) without A (fused-project blocks);
-          otherwise bn_apply(A) + wgrad + se_bn_bwd_reduce
-          SE backward (se_bwd_dz / se_bwd_dh / se_bwd_bnsum around the small fp32 GEMMs)
-          dw_bwd_uni / dw_bwd_uni_s2 (dwconv.hip): ONE pass per tile -- dy2 rebuilt from (dA, y2, gate, rb) while
-          staging (BN2-backward apply), depthwise data AND weight gradients, BN1-backward partials; expand blocks store
-          dz = dx * silu'(z) directly
-          pw_bwd_z (pwbwd.hip): dx = dz' @ We and dWe with the BN1 backward folded in through G = x^T x (y1-free)
+backward  tail_bwd_reduce (FiLM grads + BN3 partials) -> BN3 backward-apply -> dA = dy3 @ Wp, dWp, SE / BN2 sums
+          SE backward, BN2 backward-apply + depthwise data and weight gradients + BN1-backward partials
+          BN1 backward + expand data and weight gradients, residual gradient
 
-Saved per block: x, y2, y3 (bf16), y1 only outside x-mode, A only for the hipBLASLt project convs, the SE vectors
+Which kernels run each stage of a block is decided once, by ``plan_block`` (a ``BlockRoute``: one short string per
+stage), from the block's shape and the ``RouteFlags`` read from ops/switches.py; the forward plans, the backward reads
+the plan.  The comments on ``RouteFlags`` say what each path is and which log decided its default.
+
+Saved per block: x, y2, y3 (bf16), y1 only outside x-mode, A only when the project backward needs it, the SE vectors
 (pool, h, gate) and per-channel constants.
 """
 from __future__ import annotations
 
+import functools
 import os
+from dataclasses import dataclass, fields
 from typing import List, Optional
 
 import torch
@@ -79,9 +76,116 @@ def _mark(name: str):
         ev = torch.cuda.Event(enable_timing=True)
         ev.record()
         TIMING_EVENTS.append((name, ev))
-# tall-skinny MFMA kernel for wide-K / narrow-N 1x1 convs (switch pw_tall=0 routes them to hipBLASLt)
-PW_TALL = switches.on("pw_tall")
-_SHADOW = None   # data_ptr(fp32 master weight) -> bf16 view of the per-step shadow (FusedRT1.attach_flat)
+
+
+# tile tables behind RouteFlags' gemm_proj / gemm_proj_dgrad / z_gemm: (Ce, Cout) or (Ce, Cin) -> gemm.hip tile config
+_GEMM_PROJ_TILE = {(1392, 232): 1, (816, 232): 1}
+_GEMM_PROJ_DGRAD_TILE = {(1392, 232): 0, (816, 232): 0}
+_Z_GEMM_TILE = {(1392, 232): -1, (2304, 384): -1}
+
+
+@dataclass(frozen=True)
+class RouteFlags:
+    """The ops/switches.py switches that route the backbone, one field per switch of the same name.  ``FLAGS`` is the
+    process's set (``RT1_AB`` applied); ``plan_block`` turns a set and a block's shape into a ``BlockRoute``."""
+    # tall-skinny MFMA kernel for wide-K / narrow-N 1x1 convs (switch pw_tall=0 routes them to hipBLASLt)
+    pw_tall: bool
+    # the wide-N top / block-25 expand 1x1 convs (K = 384 -> N = 1536 / 2304, M = 76,800) on gemm256.hip's 256 x 256
+    # LDS-DMA tiles with the BN-statistics epilogue: 126 / 184 us against 138-164 / 196-249 us for the library,
+    # gemm.hip and pw_wide (tools/bench_gemm256.py, profiles/r5_gemm256_bench.log), and the bn_stats pass over the
+    # 1536 / 2304-wide output (61 / 94 us per step) disappears.  g256=0: the pw_wide + bn_stats path.
+    g256: bool
+    wgrad_mfma: bool
+    gram_sx: bool
+    dw_fused: bool      # fused stride-1 depthwise backward
+    # stride-2 blocks through the unified stride-2 kernel (dw_bwd_uni_s2_kernel) instead of bn_bwd_apply + data + weight
+    dw_s2_fused: bool
+    # dw_bwd_fused kernel variant: 1 = unified single-pass kernel (dw_bwd_uni_kernel), 0 = the two-pass kernel
+    dw_variant: int
+    # ... and, for the non-expand residual block 1, in the unified depthwise backward's store
+    dw_res: bool
+    pw_pro: bool        # project-conv operand prologue
+    # (not in the tall-skinny kernel of blocks 8-17: the 2 transcendentals per element make that HBM-bound GEMM
+    # VALU-bound, 0.1-0.4 ms/step slower than bn_apply + the plain kernel -- profiles/r2_pw_tall_pro_ab.log,
+    # profiles/r3_pw_tall_pro_ab.log; the kernel keeps the prologue, tests/test_pwgemm_gpu.py)
+    # project-conv backward of the skinny blocks from (dy3, y2) per frame (csrc/kernels/projbwd.hip): the SE / BN2
+    # backward sums and dWp come out of one pass, so the forward no longer stores the operand A and the backward no
+    # longer reads A (dWp) nor dA (se_bn_bwd_reduce)
+    proj_bwd: bool
+    # squeeze-excitation MLP forward / backward as the fused se.hip kernels (se_fwd / se_bwd) instead of hipBLASLt
+    # addmm/mm + elementwise launches.  The round-2 pair was 2.5-5x slower (profiles/r2_se_fused_ab.log: per-frame dot
+    # products as long dependent FMA chains on 96 workgroups); the round-3 kernels (tiled split-K row products, sliced
+    # frame reductions) beat the library path: 1278-1282 -> 1293-1295 samples/s same-box A/B (profiles/r3_se_fused_ab.log).
+    se_fused: bool
+    # Rounds 3-4 ran it on one rank only: the two-rank rehearsal (two processes on one GPU) saw SE fc1 weight gradients
+    # differ run to run.  Root cause (profiles/r4_se_dp_rootcause.md): a v_pk_fma_f32 with a high-element op_sel in
+    # se_wsum_part occasionally lost its low-lane product for 16 lanes -- dw1 came out as the exact sum minus one frame's
+    # term.  The SE kernels are now built without packed fp32 (NO_PACKED_FP32, tests/test_isa_audit.py) and the fused
+    # path is on for any world size.
+    # the stem's BatchNorm + SiLU applied inside block 0 (StemPreFn): no separate activated stem tensor
+    stem_in_block0: bool
+    # ... and the stem BN's backward-apply folded into the stem weight-gradient kernel's staging: block 0
+    # hands the stem the gradient of silu(bn(x)) plus the BN backward constants through a StemLink instead of writing
+    # the [N, 150, 150, 40] dy (one write + one read of 1.4 GB per step at b128)
+    stem_bn_bwd: bool
+    # y-free expand backward (pwbwd.hip pw_bwd_z): the unified depthwise backward stores dz = dA1 * silu'(bn1(y1)) and
+    # the expand dgrad / wgrad are rewritten over the block input x (dy1 = k1*dz + k2*(x @ We^T) + k0), so the Ce-wide
+    # y1 is not read a second time in the backward
+    pw_bwd_z: bool
+    # ... also for the wide expand convs whose dgrad runs on the tall-skinny kernel (blocks 9-17: Cin 96 / 136).  The first
+    # version (library GEMMs for x @ Mk and G, a VALU Mk kernel) measured net slower (profiles/r2_pw_z_wide_ab.log); this
+    # one folds x @ Mk + r0 into the dgrad's K loop (pw_tall_tail) and runs G on the MFMA weight-gradient kernel.
+    pw_z_wide: bool
+    # ... and for the deep blocks 19-24 (expand 232 -> 1392), whose data gradient runs on gemm.hip's two-segment kernel
+    # (gemm_tail: dz . (diag(k1) We) + x . Mk + r0 + dout * fmul in one pass).  Replaces the bn_bwd_apply pass over the
+    # Ce-wide (dA1, y1) -> dy1, the hipBLASLt dgrad of dy1 and the add_scaled_ residual pass.  (Ce, Cin) -> gemm.hip tile
+    # config (-1: automatic).  Blocks 13-18 keep the tall-skinny pw_tall_tail (faster at N = 96 / 136).  Measured
+    # step-neutral (profiles/r3_z_gemm_ab.log: 1297-1301 samples/s either way; the removed passes are paid for by the
+    # slower-than-library gemm.hip tiles at N = 232 / 384), on by default for 12 fewer launches and 7 fewer hipBLASLt
+    # GEMMs per step.  z_gemm=1 (default since the round-5 re-check, profiles/r5_switch_recheck_ab.log: +0.15 %): blocks
+    # 19-24 only; 2: also block 25's 2304 -> 384; 0: the bn_bwd_apply + library path.
+    z_gemm: str
+    # y1-free expand blocks ("x-mode", csrc/kernels/dwconv.hip stage_xmfma + xexpand.hip): the expand output y1 is never
+    # written.  BN1's batch statistics come from the block input's Gram matrix (sum y1 = We sum x, sum y1^2 = w^T G w),
+    # the depthwise forward and its unified backward recompute y1 = x @ We^T per staged tile on MFMA, and the expand
+    # backward is the dz-mode pw_bwd_z (it reads dz and x only).  Removes the expand GEMM's write of y1 and both depthwise
+    # reads of it.  The kernels cover blocks 2-8 (Cin <= 48), but the depthwise backward is VALU-issue bound and holds
+    # its K x K weight-gradient accumulators in registers: recomputing y1 there (MFMA staging, LDS for the centres) made
+    # the backward of blocks 3-8 slower than the y1 bytes it saves, so by default only block 2 (150x150 -> 75x75, 5 GB of
+    # y1 per step) runs y1-free (profiles/r3_xmode_ab.md).  xmode=all: every supported block; 0: none.
+    xmode: str
+    # BN1 of the wide expand convs (blocks 9-25: Cin 96-384 -> Ce 576-2304 on pwgemm.hip's wide kernel, no statistics
+    # epilogue) from G = x^T x and sx = sum x -- the same wgrad(x, x) / colsum(x) the dz-mode expand backward needs, now
+    # computed once in the forward and handed to the backward -- instead of a bn_stats pass over the 6x wider y1
+    # (65-130 us per block: profiles/r4_pmc_bytes.md).  gram_bn=0: the bn_stats pass.
+    gram_bn: bool
+    # Project convs of the deep blocks on the tiled MFMA GEMM (csrc/kernels/gemm.hip) with the operand prologue
+    # A = silu(bn2(y2)) * gate and the BN3-statistics epilogue: replaces bn_apply (read y2, write A) + the hipBLASLt GEMM
+    # (read A) + bn_stats (read y3); A is still stored (by the first N tile) for the weight gradient.  (Ce, Cout) -> tile
+    # config, from tools/bench_gemm_mfma.py (profiles/r3_gemm_bench.log: 1.38-1.42x over the three launches); the
+    # K = 2304 / 1392 -> 384 shapes stay on the library (0.7x).
+    gemm_proj: bool
+    # ... and their data gradients dA = dy3 @ Wp (NN; profiles/r3_gemm_bench.log "proj19 dgrad": 1.32x over hipBLASLt)
+    gemm_proj_dgrad: bool
+    # the residual path's gradient added in the wide dz-mode dgrad's epilogue instead of an add_scaled_ pass
+    tall_res: bool
+
+    @classmethod
+    def from_switches(cls, get=switches.get) -> "RouteFlags":
+        cast = {"bool": lambda v: v != "0", "int": int, "str": str}
+        return cls(**{f.name: cast[f.type](get(f.name)) for f in fields(cls)})
+
+    # the tables the switches stand for
+    g256_stats = property(lambda f: {(384, 1536), (384, 2304)} if f.g256 else set())        # (K, N)
+    gemm_proj_cfg = property(lambda f: _GEMM_PROJ_TILE if f.gemm_proj else {})
+    gemm_proj_dgrad_cfg = property(lambda f: _GEMM_PROJ_DGRAD_TILE if f.gemm_proj_dgrad else {})
+    z_gemm_cfg = property(lambda f: {"0": {}, "2": _Z_GEMM_TILE}.get(f.z_gemm, {(1392, 232): -1}))
+    # (Cin, Ce, k, s) of the y1-free blocks; None: every supported block
+    xmode_shapes = property(lambda f: {"0": set(), "all": None}.get(f.xmode, {(24, 144, 3, 2)}))
+
+
+FLAGS = RouteFlags.from_switches()
+_SHADOW = None  # data_ptr(fp32 master weight) -> bf16 view of the per-step shadow (FusedRT1.attach_flat)
 
 
 def set_weight_shadow(views):
@@ -107,33 +211,26 @@ def _lin(a: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     ext = _ext()
     if ext.pw_gemm_supported(a.shape[1], w.shape[0]):
         return ext.pw_gemm(a, w.contiguous(), _pw_blocks(a.shape[0]))[0]
-    if PW_TALL and a.shape[0] >= 4096 and ext.pw_tall_preferred(a.shape[1], w.shape[0]):
+    if FLAGS.pw_tall and a.shape[0] >= 4096 and ext.pw_tall_preferred(a.shape[1], w.shape[0]):
         # wide reduction, narrow output (project convs, expand data-gradients; N <= 144): csrc/kernels/pwtall.hip
         return ext.pw_tall(a.contiguous(), w.contiguous())[0]
     return torch.mm(a, w.t())
 
 
-# the wide-N top / block-25 expand 1x1 convs (K = 384 -> N = 1536 / 2304, M = 76,800) on gemm256.hip's 256 x 256 LDS-DMA
-# tiles with the BN-statistics epilogue: 126 / 184 us against 138-164 / 196-249 us for the library, gemm.hip and pw_wide
-# (tools/bench_gemm256.py, profiles/r5_gemm256_bench.log), and the bn_stats pass over the 1536 / 2304-wide output (61 / 94
-# us per step) disappears.  g256=0: the pw_wide + bn_stats path.
-G256_STATS = {(384, 1536), (384, 2304)} if switches.on("g256") else set()
-
-
 def _lin_bn(a: torch.Tensor, w: torch.Tensor, bnc: "BNCtx", training: bool, pro=None):
     """1x1 conv + the consumer BatchNorm's constants; in training the batch statistics come from the
     GEMM epilogue (one pass over the output) when the MFMA kernel covers the shape.  ``pro = (scale, shift, gate,
-    hw)`` makes the operand silu(a*scale + shift) * gate inside the GEMM (project convs, see project_fused)."""
+    hw)`` makes the operand silu(a*scale + shift) * gate inside the GEMM (project convs, plan_block's "pw_gemm")."""
     ext = _ext()
     if pro is not None:
-        sc, sh, gate, hw, store = pro         # project_fused: pw_gemm-supported shapes only
+        sc, sh, gate, hw, store = pro         # proj_fwd "pw_gemm": pw_gemm-supported shapes only
         res = ext.pw_gemm(a, w.contiguous(), _pw_blocks(a.shape[0]), training, sc, sh, gate, hw, store)
         consts = bnc.train_consts(res[1], res[2], a.shape[0]) if training else bnc.eval_consts()
         return res[0], consts, (res[-1] if store else None)
     if training and ext.pw_stats_supported(a.shape[1], w.shape[0]):
         y, ps, pq = ext.pw_gemm(a, w.contiguous(), _pw_blocks(a.shape[0]), True)
         return y, bnc.train_consts(ps, pq, a.shape[0])
-    if training and (a.shape[1], w.shape[0]) in G256_STATS:
+    if training and (a.shape[1], w.shape[0]) in FLAGS.g256_stats:
         y, ps, pq = ext.gemm256(a, w.contiguous(), False, stats=True, bn=256)
         return y, bnc.train_consts(ps, pq, a.shape[0])
     y = _lin(a, w)
@@ -187,53 +284,6 @@ def _wgrad_splits(M: int, out_elems: int) -> int:
     return max(1, min(S, M // 256))
 
 
-WGRAD_MFMA = switches.on("wgrad_mfma")
-DW_FUSED = switches.on("dw_fused")      # fused stride-1 depthwise backward
-
-
-PW_PRO = switches.on("pw_pro")          # project-conv operand prologue
-# (not in the tall-skinny kernel of blocks 8-17: the 2 transcendentals per element make that HBM-bound GEMM
-# VALU-bound, 0.1-0.4 ms/step slower than bn_apply + the plain kernel -- profiles/r2_pw_tall_pro_ab.log,
-# profiles/r3_pw_tall_pro_ab.log; the kernel keeps the prologue, tests/test_pwgemm_gpu.py)
-
-
-def project_fused(Ce: int, Cout: int, HW2: int) -> bool:
-    """Build the project conv's operand A = silu(bn2(y2)) * gate in the skinny GEMM's registers instead of a
-    bn_apply pass (read y2 + write A, then the GEMM reads A).  In training the GEMM also stores A for the weight
-    gradient (store_operand): rebuilding A a second time inside the wgrad kernel measured 1.8x slower there than the
-    saved pass (profiles/r2_project_prologue_ab.log), so the win is the bn_apply read of y2 and the GEMM's read of A."""
-    if not PW_PRO:
-        return False
-    ext = _ext()
-    return HW2 >= 128 and ext.pw_gemm_supported(Ce, Cout)
-
-
-# project-conv backward of the skinny blocks from (dy3, y2) per frame (csrc/kernels/projbwd.hip): the SE / BN2
-# backward sums and dWp come out of one pass, so the forward no longer stores the operand A and the backward no longer
-# reads A (dWp) nor dA (se_bn_bwd_reduce)
-PROJ_BWD = switches.on("proj_bwd")
-
-
-def proj_bwd_fused(Ce: int, Cout: int, HW2: int) -> bool:
-    return PROJ_BWD and project_fused(Ce, Cout, HW2) and _ext().proj_bwd_supported(Cout, Ce)
-
-
-# squeeze-excitation MLP forward / backward as the fused se.hip kernels (se_fwd / se_bwd) instead of hipBLASLt
-# addmm/mm + elementwise launches.  The round-2 pair was 2.5-5x slower (profiles/r2_se_fused_ab.log: per-frame dot
-# products as long dependent FMA chains on 96 workgroups); the round-3 kernels (tiled split-K row products, sliced
-# frame reductions) beat the library path: 1278-1282 -> 1293-1295 samples/s same-box A/B (profiles/r3_se_fused_ab.log).
-SE_FUSED = switches.on("se_fused")
-# Rounds 3-4 ran it on one rank only: the two-rank rehearsal (two processes on one GPU) saw SE fc1 weight gradients
-# differ run to run.  Root cause (profiles/r4_se_dp_rootcause.md): a v_pk_fma_f32 with a high-element op_sel in
-# se_wsum_part occasionally lost its low-lane product for 16 lanes -- dw1 came out as the exact sum minus one frame's
-# term.  The SE kernels are now built without packed fp32 (NO_PACKED_FP32, tests/test_isa_audit.py) and the fused
-# path is on for any world size.
-
-
-def se_fused_active() -> bool:
-    return SE_FUSED
-
-
 # RT1_SE_DEBUG=1 (tools/dp_gpu_check.py): the fused SE forward keeps copies of (pool, h, gate); the backward flags any
 # of them changed since the forward and re-runs se_bwd on the same inputs to flag a non-reproducible output.  Flags
 # are device booleans collected in SE_DEBUG_LOG (eager steps only, never inside a capture).
@@ -272,12 +322,6 @@ def _se_debug_check(ext, index: int, saved, args, outs):
         torch.save({"args": [a.detach().cpu() if torch.is_tensor(a) else a for a in args],
                     "first": outs[2].cpu(), "rerun": rerun[2].cpu()},
                    os.path.join(dump, f"se_r{rank}_b{index}_{len(os.listdir(dump))}.pt"))
-# the stem's BatchNorm + SiLU applied inside block 0 (StemPreFn): no separate activated stem tensor
-STEM_IN_BLOCK0 = switches.on("stem_in_block0")
-# ... and the stem BN's backward-apply folded into the stem weight-gradient kernel's staging: block 0
-# hands the stem the gradient of silu(bn(x)) plus the BN backward constants through a StemLink instead of writing
-# the [N, 150, 150, 40] dy (one write + one read of 1.4 GB per step at b128)
-STEM_BN_BWD_FUSED = switches.on("stem_bn_bwd")
 
 
 class StemLink:
@@ -286,90 +330,19 @@ class StemLink:
 
     def __init__(self):
         self.bn = None
-# stride-2 blocks through the unified stride-2 kernel (dw_bwd_uni_s2_kernel) instead of bn_bwd_apply + data + weight
-DW_S2_FUSED = switches.on("dw_s2_fused")
-# dw_bwd_fused kernel variant: 1 = unified single-pass kernel (dw_bwd_uni_kernel), 0 = the two-pass kernel
-DW_VARIANT = int(switches.get("dw_variant"))
-# y-free expand backward (pwbwd.hip pw_bwd_z): the unified depthwise backward stores dz = dA1 * silu'(bn1(y1)) and
-# the expand dgrad / wgrad are rewritten over the block input x (dy1 = k1*dz + k2*(x @ We^T) + k0), so the Ce-wide
-# y1 is not read a second time in the backward
-PW_BWD_Z = switches.on("pw_bwd_z")
 
 
-# ... also for the wide expand convs whose dgrad runs on the tall-skinny kernel (blocks 9-17: Cin 96 / 136).  The first
-# version (library GEMMs for x @ Mk and G, a VALU Mk kernel) measured net slower (profiles/r2_pw_z_wide_ab.log); this
-# one folds x @ Mk + r0 into the dgrad's K loop (pw_tall_tail) and runs G on the MFMA weight-gradient kernel.
-PW_Z_WIDE = switches.on("pw_z_wide")
-
-
-def pw_bwd_z_preferred(Ce: int, Cin: int, k: int, H2: int, W2: int, s: int) -> bool:
-    """dz-mode expand backward: needs the unified depthwise kernel (its BN1 epilogue stores dz); the fused pwbwd.hip
-    kernel for the high-resolution shapes, library / MFMA GEMMs around pw_z_prep / pw_z_finish for the wide ones."""
+def gram_bn_preferred(Cin: int, Ce: int, flags: RouteFlags = FLAGS) -> bool:
+    """BN1 of this expand conv from the block input's Gram moments (RouteFlags.gram_bn); plan_block's test."""
     ext = _ext()
-    if not (PW_BWD_Z and dw_fused_preferred(k, H2, W2, s) and (s == 2 or DW_VARIANT == 1)):
-        return False
-    if ext.pw_bwd_supported(Ce, Cin):
-        return True
-    if PW_Z_WIDE and z_gemm_preferred(Ce, Cin):
-        return True
-    return (PW_Z_WIDE and PW_TALL and ext.pw_tall_preferred(Ce, Cin) and wgrad_mfma_preferred(1 << 20, Cin, Cin)
-            and (Ce, Cin) not in _Z_WIDE_OFF)
-
-
-# ... and for the deep blocks 19-24 (expand 232 -> 1392), whose data gradient runs on gemm.hip's two-segment kernel
-# (gemm_tail: dz . (diag(k1) We) + x . Mk + r0 + dout * fmul in one pass).  Replaces the bn_bwd_apply pass over the
-# Ce-wide (dA1, y1) -> dy1, the hipBLASLt dgrad of dy1 and the add_scaled_ residual pass.  (Ce, Cin) -> gemm.hip tile
-# config (-1: automatic).  Blocks 13-18 keep the tall-skinny pw_tall_tail (faster at N = 96 / 136).  Measured
-# step-neutral (profiles/r3_z_gemm_ab.log: 1297-1301 samples/s either way; the removed passes are paid for by the
-# slower-than-library gemm.hip tiles at N = 232 / 384), on by default for 12 fewer launches and 7 fewer hipBLASLt
-# GEMMs per step.  z_gemm=1 (default since the round-5 re-check, profiles/r5_switch_recheck_ab.log: +0.15 %): blocks
-# 19-24 only; 2: also block 25's 2304 -> 384; 0: the bn_bwd_apply + library path.
-_ZG = switches.get("z_gemm")
-Z_GEMM = {} if _ZG == "0" else ({(1392, 232): -1, (2304, 384): -1} if _ZG == "2" else {(1392, 232): -1})
-
-
-def z_gemm_preferred(Ce: int, Cin: int) -> bool:
-    return (Ce, Cin) in Z_GEMM
-
-
-# y1-free expand blocks ("x-mode", csrc/kernels/dwconv.hip stage_xmfma + xexpand.hip): the expand output y1 is never
-# written.  BN1's batch statistics come from the block input's Gram matrix (sum y1 = We sum x, sum y1^2 = w^T G w),
-# the depthwise forward and its unified backward recompute y1 = x @ We^T per staged tile on MFMA, and the expand
-# backward is the dz-mode pw_bwd_z (it reads dz and x only).  Removes the expand GEMM's write of y1 and both depthwise
-# reads of it.  The kernels cover blocks 2-8 (Cin <= 48), but the depthwise backward is VALU-issue bound and holds
-# its K x K weight-gradient accumulators in registers: recomputing y1 there (MFMA staging, LDS for the centres) made
-# the backward of blocks 3-8 slower than the y1 bytes it saves, so by default only block 2 (150x150 -> 75x75, 5 GB of
-# y1 per step) runs y1-free (profiles/r3_xmode_ab.md).  xmode=all: every supported block; 0: none.
-_XMODE_ENV = switches.get("xmode")
-XMODE = _XMODE_ENV != "0"
-XMODE_SHAPES = None if _XMODE_ENV == "all" else {(24, 144, 3, 2)}   # (Cin, Ce, k, s)
-
-
-def x_mode_preferred(Cin: int, Ce: int, k: int, s: int, H2: int, W2: int) -> bool:
-    ext = _ext()
-    if not XMODE or (XMODE_SHAPES is not None and (Cin, Ce, k, s) not in XMODE_SHAPES):
-        return False
-    return (ext.dw_x_supported(Cin, Ce, k, s) and ext.pw_bwd_supported(Ce, Cin)
-            and pw_bwd_z_preferred(Ce, Cin, k, H2, W2, s))
-
-
-# BN1 of the wide expand convs (blocks 9-25: Cin 96-384 -> Ce 576-2304 on pwgemm.hip's wide kernel, no statistics
-# epilogue) from G = x^T x and sx = sum x -- the same wgrad(x, x) / colsum(x) the dz-mode expand backward needs, now
-# computed once in the forward and handed to the backward -- instead of a bn_stats pass over the 6x wider y1
-# (65-130 us per block: profiles/r4_pmc_bytes.md).  gram_bn=0: the bn_stats pass.
-GRAM_BN = switches.on("gram_bn")
-
-
-def gram_bn_preferred(Cin: int, Ce: int) -> bool:
-    ext = _ext()
-    return (GRAM_BN and Cin % 8 == 0 and not ext.pw_stats_supported(Cin, Ce) and ext.pw_gemm_supported(Cin, Ce)
-            and (WGRAD_MFMA and wgrad_mfma_preferred(1 << 20, Cin, Cin)))
+    return (flags.gram_bn and Cin % 8 == 0 and not ext.pw_stats_supported(Cin, Ce) and ext.pw_gemm_supported(Cin, Ce)
+            and (flags.wgrad_mfma and wgrad_mfma_preferred(1 << 20, Cin, Cin)))
 
 
 def gram_moments(x2d: torch.Tensor):
     """(G = x^T x fp32 [Cin, Cin], sx = sum_rows x fp32 [Cin]): one pass of the MFMA wgrad kernel that also sums the
     rows it stages, one fixed-order sum of both partial sets (bindings.cpp gram; ``gram_sx=0``: wgrad + colsum(x))."""
-    if not (GRAM_SX and WGRAD_MFMA and wgrad_mfma_preferred(*x2d.shape, x2d.shape[1])):
+    if not (FLAGS.gram_sx and FLAGS.wgrad_mfma and wgrad_mfma_preferred(*x2d.shape, x2d.shape[1])):
         return wgrad(x2d, x2d), _ext().colsum(x2d)
     x2d = x2d.contiguous()
     cfg = _WGRAD_TILE.get((x2d.shape[1], x2d.shape[1]))
@@ -381,9 +354,6 @@ def gram_moments(x2d: torch.Tensor):
     return G, sx
 
 
-GRAM_SX = switches.on("gram_sx")
-
-
 def gram_bn_consts(x2d: torch.Tensor, We_b: torch.Tensor, bnc: "BNCtx"):
     """Train-mode BN1 constants of y1 = x2d @ We_b^T from x2d alone: G = x^T x and sum x in one MFMA pass, the
     quadratic forms in fp64 (csrc/kernels/xexpand.hip); running stats updated in place."""
@@ -392,35 +362,15 @@ def gram_bn_consts(x2d: torch.Tensor, We_b: torch.Tensor, bnc: "BNCtx"):
                                    bn.running_var))
 
 
-# Project convs of the deep blocks on the tiled MFMA GEMM (csrc/kernels/gemm.hip) with the operand prologue
-# A = silu(bn2(y2)) * gate and the BN3-statistics epilogue: replaces bn_apply (read y2, write A) + the hipBLASLt GEMM
-# (read A) + bn_stats (read y3); A is still stored (by the first N tile) for the weight gradient.  (Ce, Cout) -> tile
-# config, from tools/bench_gemm_mfma.py (profiles/r3_gemm_bench.log: 1.38-1.42x over the three launches); the
-# K = 2304 / 1392 -> 384 shapes stay on the library (0.7x).
-GEMM_PROJ = {(1392, 232): 1, (816, 232): 1} if switches.on("gemm_proj") else {}
-
-
 def project_gemm(y2: torch.Tensor, Wp_b: torch.Tensor, sc2, sh2, gate, hw: int, bnc: "BNCtx", training: bool,
                  store_a: bool):
     """y3 = (silu(bn2(y2)) * gate) @ Wp^T with BN3's batch statistics from the epilogue -> (y3, consts, A|None)."""
     Ce = y2.shape[-1]
     M2 = y2.numel() // Ce
     res = _ext().gemm(y2.view(M2, Ce), Wp_b, False, None, sc2, sh2, gate, hw, stats=training,
-                      cfg=GEMM_PROJ[(Ce, Wp_b.shape[0])], store_a=store_a)
+                      cfg=_GEMM_PROJ_TILE[(Ce, Wp_b.shape[0])], store_a=store_a)
     consts = bnc.train_consts(res[1], res[2], M2) if training else bnc.eval_consts()
     return res[0], consts, (res[-1] if store_a else None)
-
-
-# ... and their data gradients dA = dy3 @ Wp (NN; profiles/r3_gemm_bench.log "proj19 dgrad": 1.32x over hipBLASLt)
-GEMM_PROJ_DGRAD = {(1392, 232): 0, (816, 232): 0} if switches.on("gemm_proj_dgrad") else {}
-
-
-# the residual path's gradient added in the wide dz-mode dgrad's epilogue instead of an add_scaled_ pass
-TALL_RES = switches.on("tall_res")
-# ... and, for the non-expand residual block 1, in the unified depthwise backward's store
-DW_RES = switches.on("dw_res")
-# shapes the wide dz-mode path does not pay for (filled from A/B runs)
-_Z_WIDE_OFF = set()
 
 
 def _few_splits(part: torch.Tensor) -> torch.Tensor:
@@ -430,49 +380,144 @@ def _few_splits(part: torch.Tensor) -> torch.Tensor:
     return part if part.shape[0] <= 4 else _ext().colsum(part)
 
 
-def expand_bwd_z_wide(dz: torch.Tensor, x: torch.Tensor, We: torch.Tensor, consts: torch.Tensor, res=None, gram=None):
+def expand_bwd_z_wide(dz: torch.Tensor, x: torch.Tensor, We: torch.Tensor, consts: torch.Tensor, res=None, gram=None,
+                      dgrad: str = "z_wide"):
     """Expand-conv backward of a wide block from dz [M, Ce] and the block input x [M, Cin] (y1 is not read):
     dx = dz @ (diag(k1) We) + x @ Mk + r0 and dWe = diag(k1) dz^T x + diag(k2) We G + k0 (x) sx with
     Mk = We^T diag(k2) We, G = x^T x, sx = sum_m x (csrc/kernels/pwbwd.hip pw_z_prep / pw_z_finish, pwtall.hip
     pw_tall_tail).  Replaces bn_bwd_apply (read dA1 and y1, write dy1) + the dgrad / wgrad reads of dy1 by two
     reads of dz and three of the 6x narrower x.  ``res = (dout, fmul, hw)`` adds the residual path's gradient
-    dout * fmul[frame] in the dgrad epilogue (no add_scaled_ pass)."""
+    dout * fmul[frame] in the dgrad epilogue (no add_scaled_ pass).  ``dgrad="z_gemm"``: the data gradient as one
+    two-segment GEMM on gemm.hip (csrc/kernels/gemm.hip TAIL) instead of pw_tall_tail."""
     ext = _ext()
-    wt, mk, r0 = ext.pw_z_prep(We, consts)     # (diag(k1) We)^T, We^T diag(k2) We, k0 @ We in one launch
-    if res is not None:
-        dx = ext.pw_tall_tail(dz, wt, x, mk, r0, res[0], res[1], res[2])
+    wt, mk, r0 = ext.pw_z_prep(We, consts)     # (diag(k1) We)^T [Cin, Ce], We^T diag(k2) We, k0 @ We in one launch
+    if dgrad == "z_gemm":
+        dx = ext.gemm_tail(dz, wt, x, mk, r0, *(res or ()), cfg=_Z_GEMM_TILE.get((We.shape[0], We.shape[1]), -1))
     else:
-        dx = ext.pw_tall_tail(dz, wt, x, mk, r0)
+        dx = ext.pw_tall_tail(dz, wt, x, mk, r0, *(res or ()))
     S = _few_splits(wgrad(dz, x, raw=True))  # up to 4 split partials are summed inside pw_z_finish
     G, sx = gram if gram is not None else gram_moments(x)     # from the forward's BN1 when it used them
     return dx, ext.pw_z_finish(S, G, sx, We, consts)
 
 
-def expand_bwd_z_gemm(dz: torch.Tensor, x: torch.Tensor, We: torch.Tensor, consts: torch.Tensor, res=None, gram=None):
-    """expand_bwd_z_wide with the data gradient on gemm.hip (``Z_GEMM`` shapes): dx = dz @ (diag(k1) We) + x @ Mk + r0
-    (+ dout * fmul[frame]) as one two-segment GEMM (csrc/kernels/gemm.hip TAIL); dWe as in expand_bwd_z_wide."""
-    ext = _ext()
-    wt, mk, r0 = ext.pw_z_prep(We, consts)     # wt [Cin, Ce] = (diag(k1) We)^T, mk [Cin, Cin], r0 [Cin]
-    cfg = Z_GEMM.get((We.shape[0], We.shape[1]), -1)
-    if res is not None:
-        dx = ext.gemm_tail(dz, wt, x, mk, r0, res[0], res[1], res[2], cfg)
+# shapes the wide dz-mode path does not pay for (filled from A/B runs)
+_Z_WIDE_OFF = set()
+
+
+@dataclass(frozen=True)
+class BlockRoute:
+    """The kernels one MBConv block runs, stage by stage (``plan_block``)."""
+    bn1: str            # BN1 from: "xmode" | "gram" (training) | "gemm" (epilogue or bn_stats) | "input_bn" | "none"
+    se: str             # "fused" (se.hip) | "library"
+    proj_fwd: str       # "pw_gemm" (operand prologue) | "gemm_hip" (prologue, contiguous gate) | "library" (bn_apply)
+    proj_bwd: str       # "proj_bwd" (the operand A is not stored) | "stored_a" (wgrad over A + se_bn_bwd_reduce)
+    proj_dgrad: str     # "pw_gemm_bnbwd" | "gemm_hip" | "library" (the last two after bn_bwd_apply)
+    dw_bwd: str         # "xmode" | "fused" | "unfused" (bn_bwd_apply + dw_bwd_data + dw_bwd_weight)
+    dw_variant: int     # dw_bwd_fused's stride-1 kernel: 1 unified, 0 two-pass
+    dw_blocks: int      # grid cap of the depthwise backward
+    expand_bwd: str     # "pw_bwd_z" | "z_wide" | "z_gemm" (all three read dz) | "pw_bwd" | "library" | "none"
+    pw_bwd_blocks: int  # grid cap of pw_bwd_z / pw_bwd (0 elsewhere)
+    residual: str       # the skip gradient dout * fmul is added by: "dw_bwd" | "expand_bwd" | "add_scaled" | "none"
+
+    @property
+    def zmode(self) -> bool:
+        """The depthwise backward stores dz = dA1 * silu'(bn1(y1)) for a y1-free expand backward."""
+        return self.expand_bwd in ("pw_bwd_z", "z_wide", "z_gemm")
+
+    @property
+    def dw_res(self) -> bool:
+        return self.residual == "dw_bwd"
+
+
+@functools.lru_cache(maxsize=None)
+def plan_block(spec, N: int, H: int, W: int, in_bn: bool, flags: RouteFlags = FLAGS) -> BlockRoute:
+    """Every kernel choice of block ``spec`` on an [N, H, W, in_ch] input (``in_bn``: the input is the stem conv's
+    pre-BatchNorm output), from the extension's host-side capability queries and ``flags``."""
+    ext, f = _ext(), flags
+    Cin, Ce, Cout, k, s = spec.in_ch, spec.expand_ch, spec.out_ch, spec.kernel, spec.stride
+    expand = spec.expand_ratio != 1
+    in_bn = in_bn and not expand
+    p = (k - 1) // 2
+    H2, W2 = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
+    HW2, M = H2 * W2, N * H * W
+    # depthwise backward fused or not, per layer, from tools/bench_dw_fused.py at 768 frames.  The unified kernel
+    # (profiles/r2_dw_uni_ab.log) beats the unfused sequence on every stride-1 layer, including the 19x19 k5 ones
+    # (blocks 13-17) where the two-pass kernel ran 12 % slower than unfused (profiles/r2_dw_bwd_fused_ab.log).
+    dw_fused = f.dw_fused and (f.dw_s2_fused if s == 2 else f.dw_variant != 0 or not (k == 5 and 200 <= HW2 <= 1000))
+    # dz-mode expand backward: needs the unified depthwise kernel (its BN1 epilogue stores dz); the fused pwbwd.hip
+    # kernel for the high-resolution shapes, library / MFMA GEMMs around pw_z_prep / pw_z_finish for the wide ones
+    dz_ok = expand and f.pw_bwd_z and dw_fused and (s == 2 or f.dw_variant == 1)
+    if not expand:
+        expand_bwd = "none"
+    elif dz_ok and ext.pw_bwd_supported(Ce, Cin):
+        expand_bwd = "pw_bwd_z"
+    elif dz_ok and f.pw_z_wide and (Ce, Cin) in f.z_gemm_cfg:
+        expand_bwd = "z_gemm"
+    elif (dz_ok and f.pw_z_wide and f.pw_tall and ext.pw_tall_preferred(Ce, Cin)
+          and wgrad_mfma_preferred(1 << 20, Cin, Cin) and (Ce, Cin) not in _Z_WIDE_OFF):
+        expand_bwd = "z_wide"
+    elif ext.pw_bwd_supported(Ce, Cin):
+        expand_bwd = "pw_bwd"       # SiLU/BN1 backward + dgrad + wgrad over the stored y1 in one pass
     else:
-        dx = ext.gemm_tail(dz, wt, x, mk, r0, cfg=cfg)
-    S = _few_splits(wgrad(dz, x, raw=True))  # up to 4 split partials are summed inside pw_z_finish
-    G, sx = gram if gram is not None else gram_moments(x)     # from the forward's BN1 when it used them
-    return dx, ext.pw_z_finish(S, G, sx, We, consts)
+        expand_bwd = "library"      # bn_bwd_apply, then library / MFMA dgrad and wgrad
+    xmode = (expand_bwd == "pw_bwd_z" and (f.xmode_shapes is None or (Cin, Ce, k, s) in f.xmode_shapes)
+             and ext.dw_x_supported(Cin, Ce, k, s))
+    if xmode:
+        bn1 = "xmode"
+    elif expand:
+        bn1 = "gram" if gram_bn_preferred(Cin, Ce, f) else "gemm"
+    else:
+        bn1 = "input_bn" if in_bn else "none"
+    # Project conv with its operand A = silu(bn2(y2)) * gate built in the skinny GEMM's registers instead of a
+    # bn_apply pass (read y2 + write A, then the GEMM reads A).  In training the GEMM also stores A for the weight
+    # gradient (store_operand) unless proj_bwd runs: rebuilding A a second time inside the wgrad kernel measured 1.8x
+    # slower there than the saved pass (profiles/r2_project_prologue_ab.log).
+    pro = f.pw_pro and HW2 >= 128 and ext.pw_gemm_supported(Ce, Cout)
+    proj_fwd = "pw_gemm" if pro else ("gemm_hip" if (Ce, Cout) in f.gemm_proj_cfg else "library")
+    proj_bwd = "proj_bwd" if (pro and f.proj_bwd and ext.proj_bwd_supported(Cout, Ce)) else "stored_a"
+    proj_dgrad = ("gemm_hip" if (Ce, Cout) in f.gemm_proj_dgrad_cfg else
+                  "pw_gemm_bnbwd" if ext.pw_gemm_bnbwd_supported(Cout, Ce) else "library")
+    if xmode:
+        dw_bwd, dw_blocks = "xmode", XMODE_BLOCKS
+    elif dw_fused:
+        dw_bwd, dw_blocks = "fused", _DW_BWD_BLOCKS.get((H2, Ce), MAX_BLOCKS)
+    else:
+        dw_bwd, dw_blocks = "unfused", MAX_BLOCKS
+    if not spec.has_skip:
+        residual = "none"
+    elif dw_bwd == "fused" and f.dw_res and f.dw_variant != 0 and not (expand or in_bn):
+        residual = "dw_bwd"         # a skip block is stride 1: the unified stride-1 kernel's store
+    elif expand_bwd in ("pw_bwd_z", "pw_bwd") or (expand_bwd in ("z_wide", "z_gemm") and f.tall_res):
+        residual = "expand_bwd"
+    else:
+        residual = "add_scaled"
+    pw_bwd_blocks = _pw_bwd_blocks(M, z=expand_bwd == "pw_bwd_z") if expand_bwd in ("pw_bwd_z", "pw_bwd") else 0
+    return BlockRoute(bn1, "fused" if f.se_fused else "library", proj_fwd, proj_bwd, proj_dgrad, dw_bwd, f.dw_variant,
+                      dw_blocks, expand_bwd, pw_bwd_blocks, residual)
 
 
-def dw_fused_preferred(k: int, H: int, W: int, s: int = 1) -> bool:
-    """Per-layer choice between dw_bwd_fused and the unfused sequence, from tools/bench_dw_fused.py at 768 frames.
-    The unified kernel (profiles/r2_dw_uni_ab.log) beats the unfused sequence on every stride-1 layer, including the
-    19x19 k5 ones (blocks 13-17) where the two-pass kernel ran 12 % slower than unfused
-    (profiles/r2_dw_bwd_fused_ab.log)."""
-    if not DW_FUSED:
-        return False
-    if s == 2:
-        return DW_S2_FUSED
-    return DW_VARIANT != 0 or not (k == 5 and 200 <= H * W <= 1000)
+@dataclass
+class BlockMeta:
+    """Non-tensor arguments of MBConvFn.  ``in_consts``: input-BN mode (block 0 after StemPreFn) -- x is the stem conv
+    output BEFORE its BatchNorm, (sc, sh, mean, rstd) of that BN arrive here, its gamma / beta in the g1 / b1 slots,
+    and the block applies BN + SiLU in the depthwise staging exactly as it applies BN1 to an expand conv's output.
+    ``route``: run this BlockRoute instead of plan_block's (tests run the non-default routes in-process this way)."""
+    spec: object
+    bns: list
+    training: bool
+    in_consts: Optional[tuple] = None
+    stem_link: Optional[StemLink] = None
+    route: Optional[BlockRoute] = None
+
+
+def _opt(t: Optional[torch.Tensor]) -> torch.Tensor:
+    """An absent saved tensor as an empty one ..."""
+    return t if t is not None else torch.empty(0)
+
+
+def _unopt(t: torch.Tensor) -> Optional[torch.Tensor]:
+    """... and back."""
+    return t if t.numel() else None
 
 
 def wgrad(dy: torch.Tensor, x: torch.Tensor, prologue=None, final: bool = False, ok: bool = True,
@@ -485,7 +530,7 @@ def wgrad(dy: torch.Tensor, x: torch.Tensor, prologue=None, final: bool = False,
     that sums them (pw_z_finish)."""
     ext = _ext()
     final = final or raw
-    if prologue is not None or (WGRAD_MFMA and wgrad_mfma_preferred(dy.shape[0], dy.shape[1], x.shape[1])):
+    if prologue is not None or (FLAGS.wgrad_mfma and wgrad_mfma_preferred(dy.shape[0], dy.shape[1], x.shape[1])):
         dy, x = dy.contiguous(), x.contiguous()
         if prologue is None:
             cfg = _WGRAD_TILE.get((dy.shape[1], x.shape[1]))
@@ -608,15 +653,14 @@ class StemFn(torch.autograd.Function):
         else:
             sc, sh, mu, rs = bnc.eval_consts()
         a = ext.bn_apply(y, sc, sh, ACT_SILU, None, 0)
-        ctx.save_for_backward(img, shift if shift is not None else torch.empty(0), y, sc, sh, mu, rs, gamma)
-        ctx.has_shift = shift is not None
+        ctx.save_for_backward(img, _opt(shift), y, sc, sh, mu, rs, gamma)
         return a
 
     @staticmethod
     def backward(ctx, da):
         ext = _ext()
         img, shift, y, sc, sh, mu, rs, gamma = ctx.saved_tensors
-        shift = shift if ctx.has_shift else None
+        shift = _unopt(shift)
         da = da.contiguous()
         M = y.numel() // 40
         pa, pb = ext.bn_bwd_reduce(da, None, None, 0, y, sc, sh, mu, rs, ACT_SILU, _partials(M))
@@ -639,8 +683,7 @@ class StemPreFn(torch.autograd.Function):
         y, ps, pq = ext.stem_fwd(img, shift, w.reshape(40, 27).float().contiguous(), STEM_FWD_BLOCKS)
         M = y.numel() // 40
         sc, sh, mu, rs = bnc.train_consts(ps, pq, M) if training else bnc.eval_consts()
-        ctx.save_for_backward(img, shift if shift is not None else torch.empty(0))
-        ctx.has_shift = shift is not None
+        ctx.save_for_backward(img, _opt(shift))
         ctx.link = link
         ctx.mark_non_differentiable(sc, sh, mu, rs)
         ctx.set_materialize_grads(False)        # no zero-filled gradients for the four constants
@@ -649,8 +692,7 @@ class StemPreFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy, *_):
         ext = _ext()
-        img, shift = ctx.saved_tensors
-        shift = shift if ctx.has_shift else None
+        img, shift = map(_unopt, ctx.saved_tensors)
         link = ctx.link
         if link is not None and link.bn is not None:
             # dy is the gradient of silu(bn(y)); the BN backward-apply runs in the kernel's staging
@@ -664,78 +706,62 @@ class StemPreFn(torch.autograd.Function):
 
 class MBConvFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, fmul, fadd, keep, We, g1, b1, Wd, g2, b2, f1w, f1b, f2w, f2b, Wp, g3, b3, meta):
+    def forward(ctx, x, fmul, fadd, keep, We, g1, b1, Wd, g2, b2, f1w, f1b, f2w, f2b, Wp, g3, b3, meta: BlockMeta):
         ext = _ext()
-        spec, bns, training = meta[:3]
-        # input-BN mode (block 0 after StemPreFn): x is the stem conv output BEFORE its BatchNorm; (sc, sh, mean,
-        # rstd) of that BN arrive in meta, its gamma / beta in the g1 / b1 slots, and the block applies BN + SiLU in
-        # the depthwise staging exactly as it applies BN1 to an expand conv's output
-        in_consts = meta[3] if len(meta) > 3 else None
+        spec, bns, training = meta.spec, meta.bns, meta.training
         _mark(f"fwd{spec.index}")
         N, H, W, Cin = x.shape
         Ce, Cout, k, s = spec.expand_ch, spec.out_ch, spec.kernel, spec.stride
         M = N * H * W
         expand = We is not None
-        in_bn = in_consts is not None and not expand
-        p_ = (k - 1) // 2
-        H2_, W2_ = (H + 2 * p_ - k) // s + 1, (W + 2 * p_ - k) // s + 1
-        xmode = expand and x_mode_preferred(Cin, Ce, k, s, H2_, W2_)
+        in_bn = meta.in_consts is not None and not expand
+        r = meta.route if meta.route is not None else plan_block(spec, N, H, W, in_bn)
+        if expand != (r.expand_bwd != "none") or in_bn != (r.bn1 == "input_bn"):
+            raise ValueError(f"block {spec.index}: {r} was not planned for this block (expand {expand}, in_bn {in_bn})")
+        # ---- expand 1x1 + BN1 constants
+        y1 = sc1 = sh1 = mu1 = rs1 = None
         gram = None                     # (x^T x, sum x) when BN1 came from them: reused by the dz-mode backward
-        if xmode:
-            # y1 = x @ We^T is never materialised (see XMODE): BN1 from x's Gram matrix, y1 rebuilt in dw_fwd_x
-            We_b = _bf(We).reshape(Ce, Cin).contiguous()
-            if training:
-                sc1, sh1, mu1, rs1 = gram_bn_consts(x.view(M, Cin), We_b, bns[0])
-            else:
-                sc1, sh1, mu1, rs1 = bns[0].eval_consts()
-            y1 = None
-            dw_in, dsc, dsh, dact = None, sc1, sh1, ACT_SILU
-        elif expand and training and gram_bn_preferred(Cin, Ce):
-            We_b = _bf(We).reshape(Ce, Cin).contiguous()
+        We_b = _bf(We).reshape(Ce, Cin).contiguous() if expand else None
+        bn1 = "gemm" if (r.bn1 == "gram" and not training) else r.bn1
+        if bn1 == "xmode":
+            # y1 = x @ We^T is never materialised: BN1 from x's Gram matrix, y1 rebuilt in dw_fwd_x
+            sc1, sh1, mu1, rs1 = (gram_bn_consts(x.view(M, Cin), We_b, bns[0]) if training else bns[0].eval_consts())
+        elif bn1 == "gram":
             y1 = _lin(x.view(M, Cin), We_b).view(N, H, W, Ce)
             gram = gram_moments(x.view(M, Cin))
             bn = bns[0].bn
             sc1, sh1, mu1, rs1 = ext.bn_from_gram(gram[0], gram[1], We_b, float(M), bn.weight, bn.bias, bn.eps,
                                                   bn.momentum, bn.running_mean, bn.running_var)
-            dw_in, dsc, dsh, dact = y1, sc1, sh1, ACT_SILU
-        elif expand:
-            y1, (sc1, sh1, mu1, rs1) = _lin_bn(x.view(M, Cin), _bf(We).reshape(Ce, Cin), bns[0], training)
+        elif bn1 == "gemm":
+            y1, (sc1, sh1, mu1, rs1) = _lin_bn(x.view(M, Cin), We_b, bns[0], training)
             y1 = y1.view(N, H, W, Ce)
-            dw_in, dsc, dsh, dact = y1, sc1, sh1, ACT_SILU
-        elif in_bn:
+        elif bn1 == "input_bn":
             if spec.has_skip:
                 raise ValueError("input-BN mode needs a block without a residual (its input is pre-activation)")
-            y1 = None
-            sc1, sh1, mu1, rs1 = in_consts
-            dw_in, dsc, dsh, dact = x, sc1, sh1, ACT_SILU
+            sc1, sh1, mu1, rs1 = meta.in_consts
+        # ---- depthwise + BN2 constants: BN1 + SiLU applied while staging
+        wd = Wd.reshape(Ce, k * k).float().contiguous()
+        if bn1 == "xmode":
+            y2, ps2, pq2 = ext.dw_fwd_x(x, We_b, wd, sc1, sh1, k, s, XMODE_BLOCKS)
         else:
-            y1 = sc1 = sh1 = mu1 = rs1 = None
-            dw_in, dsc, dsh, dact = x, None, None, ACT_NONE
+            y2, ps2, pq2 = ext.dw_fwd(y1 if expand else x, wd, sc1, sh1, ACT_SILU if sc1 is not None else ACT_NONE,
+                                      k, s, MAX_BLOCKS)
         bn2, bn3 = bns[-2], bns[-1]
-        if xmode:
-            y2, ps2, pq2 = ext.dw_fwd_x(x, We_b, Wd.reshape(Ce, k * k).float().contiguous(), sc1, sh1, k, s,
-                                        XMODE_BLOCKS)
-        else:
-            y2, ps2, pq2 = ext.dw_fwd(dw_in, Wd.reshape(Ce, k * k).float().contiguous(), dsc, dsh, dact, k, s,
-                                      MAX_BLOCKS)
         _, H2, W2, _ = y2.shape
         HW2 = H2 * W2
         M2 = N * HW2
-        if training:
-            sc2, sh2, mu2, rs2 = bn2.train_consts(ps2, pq2, M2)
-        else:
-            sc2, sh2, mu2, rs2 = bn2.eval_consts()
-        # squeeze-excitation (fp32, [N, Ce])
+        sc2, sh2, mu2, rs2 = bn2.train_consts(ps2, pq2, M2) if training else bn2.eval_consts()
+        # ---- squeeze-excitation (fp32, [N, Ce])
         se = spec.se_ch
         f1 = f1w.reshape(se, Ce).float()
         f2 = f2w.reshape(Ce, se).float()
-        if se_fused_active():
+        hs = None
+        if r.se == "fused":
             # pool sum -> fc1 -> SiLU -> fc2 -> sigmoid in two kernels (csrc/kernels/se.hip se_rowdot + se_rowmat);
             # the returned pool is the frame SUM (the backward applies 1/HW)
             pool, h, gate = ext.se_fwd(ext.frame_pool(y2.view(N, HW2, Ce), None, sc2, sh2, ACT_SILU), 1.0 / HW2,
                                        f1.contiguous(), f1b.float().contiguous(), f2.contiguous(),
                                        f2b.float().contiguous())
-            hs = torch.empty(0, device=x.device)
             if _SE_DEBUG and not torch.cuda.is_current_stream_capturing():
                 ctx.se_dbg = (pool.clone(), h.clone(), gate.clone())
         else:
@@ -745,13 +771,13 @@ class MBConvFn(torch.autograd.Function):
             hs = F.silu(h)
             z = torch.addmm(f2b.float(), hs, f2.t())
             gate = torch.sigmoid(z).contiguous()
-        if project_fused(Ce, Cout, HW2):
-            # operand rebuilt in the GEMM's registers; stored (for dWp) only when a backward will follow
-            need_a = (training or Wp.requires_grad or x.requires_grad) and not proj_bwd_fused(Ce, Cout, HW2)
+        # ---- project 1x1 + BN3 constants; the operand A is stored (for dWp) only when a backward will read it
+        need_a = training or Wp.requires_grad or x.requires_grad
+        proj = "library" if (r.proj_fwd == "gemm_hip" and not gate.is_contiguous()) else r.proj_fwd
+        if proj == "pw_gemm":
             y3, (sc3, sh3, mu3, rs3), A = _lin_bn(y2.view(M2, Ce), _bf(Wp).reshape(Cout, Ce), bn3, training,
-                                                  pro=(sc2, sh2, gate, HW2, need_a))
-        elif (Ce, Cout) in GEMM_PROJ and HW2 >= 1 and gate.is_contiguous():
-            need_a = training or Wp.requires_grad or x.requires_grad
+                                                  pro=(sc2, sh2, gate, HW2, need_a and r.proj_bwd != "proj_bwd"))
+        elif proj == "gemm_hip":
             y3, (sc3, sh3, mu3, rs3), A = project_gemm(y2, _bf(Wp).reshape(Cout, Ce).contiguous(), sc2, sh2, gate,
                                                        HW2, bn3, training, need_a)
         else:
@@ -761,26 +787,23 @@ class MBConvFn(torch.autograd.Function):
         keep_t = keep if (keep is not None and spec.has_skip) else None
         out = ext.block_tail(y3.view(N, HW2, Cout), sc3, sh3, keep_t, skip.view(N, HW2, Cout) if skip is not None
                              else None, fmul, fadd)
-        ctx.meta = (spec, expand, (N, H, W, Cin, H2, W2), keep_t is not None, in_bn, xmode)
-        ctx.gram = gram
-        ctx.stem_link = meta[4] if (in_bn and len(meta) > 4) else None
-        ctx.save_for_backward(x, fmul, keep_t if keep_t is not None else torch.empty(0), We if expand else torch.empty(0),
-                              g1 if (expand or in_bn) else torch.empty(0), Wd, g2, f1w, f2w, Wp, g3,
-                              y1 if y1 is not None else torch.empty(0), y2, A if A is not None else torch.empty(0), y3,
-                              gate, pool, h, hs,
-                              *(t if t is not None else torch.empty(0) for t in (sc1, sh1, mu1, rs1)),
-                              sc2, sh2, mu2, rs2, sc3, sh3, mu3, rs3)
+        ctx.spec, ctx.route, ctx.shape, ctx.gram = spec, r, (N, H, W, Cin, H2, W2), gram
+        ctx.stem_link = meta.stem_link if in_bn else None
+        ctx.save_for_backward(x, fmul, Wd, g2, f1w, f2w, Wp, g3, y2, y3, gate, pool, h, sc2, sh2, mu2, rs2, sc3, sh3,
+                              mu3, rs3, *map(_opt, (keep_t, We, g1 if (expand or in_bn) else None, y1, A, hs, sc1,
+                                                    sh1, mu1, rs1)))
         _mark(f"fwd{spec.index}_end")
         return out.view(N, H2, W2, Cout)
 
     @staticmethod
     def backward(ctx, dout):
         ext = _ext()
-        spec, expand, (N, H, W, Cin, H2, W2), has_keep, in_bn, xmode = ctx.meta
+        spec, r, (N, H, W, Cin, H2, W2) = ctx.spec, ctx.route, ctx.shape
         _mark(f"bwd{spec.index}")
-        (x, fmul, keep, We, g1, Wd, g2, f1w, f2w, Wp, g3, y1, y2, A, y3, gate, pool, h, hs,
-         sc1, sh1, mu1, rs1, sc2, sh2, mu2, rs2, sc3, sh3, mu3, rs3) = ctx.saved_tensors
-        keep = keep if has_keep else None
+        (x, fmul, Wd, g2, f1w, f2w, Wp, g3, y2, y3, gate, pool, h, sc2, sh2, mu2, rs2, sc3, sh3, mu3, rs3,
+         *absent) = ctx.saved_tensors
+        keep, We, g1, y1, A, hs, sc1, sh1, mu1, rs1 = map(_unopt, absent)
+        gram, ctx.gram = ctx.gram, None
         Ce, Cout, k, s, se = spec.expand_ch, spec.out_ch, spec.kernel, spec.stride, spec.se_ch
         HW2 = H2 * W2
         M, M2 = N * H * W, N * H2 * W2
@@ -793,9 +816,8 @@ class MBConvFn(torch.autograd.Function):
         mdz3, mdzx3, dg3, db3 = ext.bn_bwd_finalize_new(pdz3, pdzx3, float(M2))
         # ---- BN3 backward-apply + project data gradient
         Wp2 = _bf(Wp).reshape(Cout, Ce)
-        pbf = A.numel() == 0 and proj_bwd_fused(Ce, Cout, HW2)
         kp = keep.float().contiguous() if keep is not None else None
-        if (Ce, Cout) not in GEMM_PROJ_DGRAD and ext.pw_gemm_bnbwd_supported(Cout, Ce):
+        if r.proj_dgrad == "pw_gemm_bnbwd":
             # blocks 0-7: dy3 = BN3-backward(dout, y3) is built in the skinny GEMM's operand prologue and stored once
             # for the project weight gradient (no bn_bwd_apply launch, no second read of dy3)
             dA, dy3 = ext.pw_gemm_bnbwd(dout.view(M2, Cout), y3.view(M2, Cout), Wp2.t().contiguous(), fmul, kp, HW2,
@@ -804,27 +826,28 @@ class MBConvFn(torch.autograd.Function):
             # the drop-path mask scales the FiLM row multiplier inside the kernel (fmul * keep[frame])
             dy3 = ext.bn_bwd_apply(dout.view(M2, Cout), fmul, None, HW2, y3, sc3, sh3, mu3, rs3,
                                    g3.float().contiguous(), ACT_NONE, mdz3, mdzx3, kp)
-            if (Ce, Cout) in GEMM_PROJ_DGRAD:
-                dA = ext.gemm(dy3.view(M2, Cout), Wp2.contiguous(), True, cfg=GEMM_PROJ_DGRAD[(Ce, Cout)])[0]
+            if r.proj_dgrad == "gemm_hip":
+                dA = ext.gemm(dy3.view(M2, Cout), Wp2.contiguous(), True, cfg=_GEMM_PROJ_DGRAD_TILE[(Ce, Cout)])[0]
             else:
                 dA = _lin(dy3, Wp2.t())                                          # [M2, Ce]
-        if pbf:
+        # ---- project weight gradient, squeeze-excitation + BN2 backward statistics
+        if A is None and r.proj_bwd == "proj_bwd":
             # SE + BN2 backward sums and dWp from (dy3, y2) in one pass per frame, the dA-weighted sums contracted
             # through dA = dy3 @ Wp (csrc/kernels/projbwd.hip); the operand A was never stored
             red, dWp = ext.proj_bwd(dy3, y2.view(N, HW2, Ce), Wp2.contiguous(), gate, sc2, sh2, mu2, rs2)
             dWp = dWp.view_as(Wp)
         else:
-            if A.numel() == 0:                    # forward ran without storing the operand
+            if A is None:                         # forward ran without storing the operand
                 A = ext.bn_apply(y2, sc2, sh2, ACT_SILU, gate, HW2)
             dWp = wgrad(dy3, A.view(M2, Ce), final=True, ok=ctx.needs_input_grad[14]).view_as(Wp)
-            # ---- squeeze-excitation + BN2 backward statistics: ONE pass over (dA, y2)
+            # ONE pass over (dA, y2)
             red = ext.se_bn_bwd_reduce(dA.view(N, HW2, Ce), y2.view(N, HW2, Ce), sc2, sh2, mu2, rs2)  # [5, N, Ce]
         f1 = f1w.reshape(se, Ce).float()
         f2 = f2w.reshape(Ce, se).float()
         # SE + BN2 backward glue in three kernels around the four small GEMMs (csrc/kernels/se.hip):
         #   dz = sum_hw(dA * a2) * g(1-g);  dh = (dz f2) * silu'(h);  rb = (dh f1) / HW (grad of a2 via the pool);
         #   BN2 sums: sum dz = sum_n gate*S1 + rb*S2,  sum dz*xhat = sum_n gate*S3 + rb*S4
-        if se_fused_active():
+        if r.se == "fused":
             # per-frame chain + reductions over frames in two kernels (se_bwd_frame, se_bwd_wsum)
             df2w, df2b, df1w, df1b, rb, db2, dg2, mdz2, mdzx2 = ext.se_bwd(red, gate, h, pool, 1.0 / HW2,
                                                                           f1.contiguous(), f2.contiguous(), float(M2))
@@ -841,106 +864,71 @@ class MBConvFn(torch.autograd.Function):
             dh, df1b = ext.se_bwd_dh(dz @ f2, h)
             df1w = torch.addmm(_scalar_zero(dev), dh.t(), pool, beta=0.0, alpha=1.0 / HW2).view_as(f1w)
             rb, db2, dg2, mdz2, mdzx2 = ext.se_bwd_bnsum(red, gate, dh @ f1, 1.0 / HW2, float(M2))
+        # ---- BN2 backward-apply + depthwise backward -> d1: gradient of the depthwise input (dz in zmode), bn1p: the
+        # BN1-backward partials when that input is BN + SiLU of a pre-activation tensor (y1, or x in input-BN mode)
         wd = Wd.reshape(Ce, k * k).float().contiguous()
-        pre = expand or in_bn          # the depthwise input is BN + SiLU of a stored pre-activation tensor
-        x1 = y1 if expand else x
-        zmode = expand and (xmode or pw_bwd_z_preferred(Ce, Cin, k, H2, W2, s))
-        skip_done = False
-        if xmode:
+        pre = sc1 is not None
+        x1 = y1 if y1 is not None else x
+        if r.dw_bwd == "xmode":
             # y1 recomputed per tile from (x, We) on MFMA; the kernel stores dz for pw_bwd_z
             res = ext.dw_bwd_fused_x(dA.view(N, H2, W2, Ce), y2, gate, rb.contiguous(), sc2, sh2, mu2, rs2,
                                      g2.float().contiguous(), mdz2, mdzx2, wd, k, x, _bf(We).reshape(Ce, Cin).contiguous(),
-                                     sc1, sh1, mu1, rs1, XMODE_BLOCKS, True)
-            dy2 = None
-            dWd = res[1].view_as(Wd)
-            dA1, pa1, pb1 = res[0], res[2], res[3]
-        elif dw_fused_preferred(k, H2, W2, s):
+                                     sc1, sh1, mu1, rs1, r.dw_blocks, True)
+            d1, dWd, bn1p = res[0], res[1].view_as(Wd), res[2:4]
+        elif r.dw_bwd == "fused":
             # BN2 backward-apply + depthwise data AND weight gradients in one pass; dy2 never reaches HBM
             # (csrc/kernels/dwconv.hip dw_bwd_uni_kernel / dw_bwd_uni_s2_kernel)
             # non-expand residual block (block 1): the residual gradient dout * fmul joins dx in the kernel's store
-            dw_res = DW_RES and not pre and spec.has_skip and s == 1 and DW_VARIANT != 0
             res = ext.dw_bwd_fused(dA.view(N, H2, W2, Ce), y2, gate, rb.contiguous(), sc2, sh2, mu2, rs2,
-                                   g2.float().contiguous(), mdz2, mdzx2, wd, k, x1,
-                                   sc1 if pre else None, sh1 if pre else None,
-                                   ACT_SILU if pre else ACT_NONE, mu1 if pre else None,
-                                   rs1 if pre else None, _DW_BWD_BLOCKS.get((H2, Ce), MAX_BLOCKS), DW_VARIANT, zmode,
-                                   dout.view(N, H, W, Cin) if dw_res else None,
-                                   fmul.float().contiguous() if dw_res else None)
-            skip_done = dw_res
-            dy2 = None
-            dWd = res[1].view_as(Wd)
-            if pre:
-                dA1, pa1, pb1 = res[0], res[2], res[3]
-            else:
-                dx = res[0]
+                                   g2.float().contiguous(), mdz2, mdzx2, wd, k, x1, sc1, sh1,
+                                   ACT_SILU if pre else ACT_NONE, mu1, rs1, r.dw_blocks, r.dw_variant, r.zmode,
+                                   dout.view(N, H, W, Cin) if r.dw_res else None,
+                                   fmul.float().contiguous() if r.dw_res else None)
+            d1, dWd, bn1p = res[0], res[1].view_as(Wd), res[2:4]
         else:
             dy2 = ext.bn_bwd_apply(dA, gate, rb, HW2, y2, sc2, sh2, mu2, rs2, g2.float().contiguous(), ACT_SILU,
                                    mdz2, mdzx2).view(N, H2, W2, Ce)
-        # ---- depthwise backward
-        if expand:
-            if dy2 is not None:
-                dA1, pa1, pb1 = ext.dw_bwd_data(dy2, wd, H, W, k, s, y1, sc1, sh1, mu1, rs1, MAX_BLOCKS)
-                dWd = ext.dw_bwd_weight(dy2, y1, sc1, sh1, ACT_SILU, k, s, _dw_wgrad_blocks(Ce)).view_as(Wd)
-            if zmode and not ext.pw_bwd_supported(Ce, Cin):
-                mdz1, mdzx1, dg1, db1, consts = ext.bn_bwd_finalize_pw(pa1, pb1, float(M), sc1, sh1,
-                                                                       g1.float().contiguous(), mu1, rs1)
-                res = spec.has_skip and TALL_RES
-                zfn = expand_bwd_z_gemm if z_gemm_preferred(Ce, Cin) else expand_bwd_z_wide
-                dx2, dWe = zfn(dA1.view(M, Ce), x.view(M, Cin), _bf(We).reshape(Ce, Cin), consts.contiguous(),
-                               (dout.view(M, Cin), fmul.float().contiguous(), H * W) if res else None, ctx.gram)
-                ctx.gram = None
-                dx = dx2.view(N, H, W, Cin)
-                dWe = dWe.view_as(We)
-                skip_done = res
-            elif zmode:
-                # dA1 holds dz = dA1 * silu'(bn1(y1)); dgrad / wgrad over x instead of y1 (csrc/kernels/pwbwd.hip)
-                mdz1, mdzx1, dg1, db1, consts = ext.bn_bwd_finalize_pw(pa1, pb1, float(M), sc1, sh1,
-                                                                       g1.float().contiguous(), mu1, rs1)
-                res = spec.has_skip
-                dx2, dWe = ext.pw_bwd_z(dA1.view(M, Ce), x.view(M, Cin), _bf(We).reshape(Ce, Cin), consts.contiguous(),
-                                        dout.view(M, Cin) if res else None, fmul.float().contiguous() if res else None,
-                                        H * W, _pw_bwd_blocks(M, z=True))
-                dx = dx2.view(N, H, W, Cin)
-                dWe = dWe.view_as(We)
-                skip_done = res
-            elif ext.pw_bwd_supported(Ce, Cin):
-                # SiLU/BN1 backward + dgrad + wgrad of the expand conv in ONE pass (csrc/kernels/pwbwd.hip); its five
-                # per-channel constants come out of the BN1 finalize launch
-                mdz1, mdzx1, dg1, db1, consts = ext.bn_bwd_finalize_pw(pa1, pb1, float(M), sc1, sh1,
-                                                                       g1.float().contiguous(), mu1, rs1)
-                res = spec.has_skip
-                dx2, dWe = ext.pw_bwd(dA1.view(M, Ce), y1.view(M, Ce), x.view(M, Cin), _bf(We).reshape(Ce, Cin),
-                                      consts.contiguous(), dout.view(M, Cin) if res else None,
-                                      fmul.float().contiguous() if res else None, H * W, _pw_bwd_blocks(M))
-                dx = dx2.view(N, H, W, Cin)
-                dWe = dWe.view_as(We)
-                skip_done = res
+            d1, *bn1p = ext.dw_bwd_data(dy2, wd, H, W, k, s, x1 if pre else None, sc1, sh1, mu1, rs1, r.dw_blocks)
+            dWd = ext.dw_bwd_weight(dy2, x1, sc1, sh1, ACT_SILU if pre else ACT_NONE, k, s,
+                                    _dw_wgrad_blocks(Ce)).view_as(Wd)
+        # ---- BN1 backward + expand backward
+        dg1 = db1 = dWe = None
+        if r.expand_bwd == "library":
+            mdz1, mdzx1, dg1, db1 = ext.bn_bwd_finalize_new(bn1p[0], bn1p[1], float(M))
+            dy1 = ext.bn_bwd_apply(d1, None, None, 0, y1, sc1, sh1, mu1, rs1, g1.float().contiguous(), ACT_SILU,
+                                   mdz1, mdzx1).view(M, Ce)
+            dx = _lin(dy1, _bf(We).reshape(Ce, Cin).t()).view(N, H, W, Cin)
+            dWe = wgrad(dy1, x.view(M, Cin), final=True, ok=ctx.needs_input_grad[4]).view_as(We)
+        elif r.expand_bwd != "none":
+            # SiLU/BN1 backward + dgrad + wgrad of the expand conv in ONE pass; the five per-channel constants come
+            # out of the BN1 finalize launch
+            mdz1, mdzx1, dg1, db1, consts = ext.bn_bwd_finalize_pw(bn1p[0], bn1p[1], float(M), sc1, sh1,
+                                                                   g1.float().contiguous(), mu1, rs1)
+            We_b, consts = _bf(We).reshape(Ce, Cin), consts.contiguous()
+            rd, rf = (dout.view(M, Cin), fmul.float().contiguous()) if r.residual == "expand_bwd" else (None, None)
+            if r.expand_bwd == "pw_bwd_z":
+                # d1 holds dz = dA1 * silu'(bn1(y1)); dgrad / wgrad over x instead of y1 (csrc/kernels/pwbwd.hip)
+                dx, dWe = ext.pw_bwd_z(d1.view(M, Ce), x.view(M, Cin), We_b, consts, rd, rf, H * W, r.pw_bwd_blocks)
+            elif r.expand_bwd == "pw_bwd":
+                dx, dWe = ext.pw_bwd(d1.view(M, Ce), y1.view(M, Ce), x.view(M, Cin), We_b, consts, rd, rf, H * W,
+                                     r.pw_bwd_blocks)
             else:
-                mdz1, mdzx1, dg1, db1 = ext.bn_bwd_finalize_new(pa1, pb1, float(M))
-                dy1 = ext.bn_bwd_apply(dA1, None, None, 0, y1, sc1, sh1, mu1, rs1, g1.float().contiguous(), ACT_SILU,
-                                       mdz1, mdzx1).view(M, Ce)
-                dx = _lin(dy1, _bf(We).reshape(Ce, Cin).t()).view(N, H, W, Cin)
-                dWe = wgrad(dy1, x.view(M, Cin), final=True, ok=ctx.needs_input_grad[4]).view_as(We)
-        elif in_bn:
-            if dy2 is not None:
-                dA1, pa1, pb1 = ext.dw_bwd_data(dy2, wd, H, W, k, s, x, sc1, sh1, mu1, rs1, MAX_BLOCKS)
-                dWd = ext.dw_bwd_weight(dy2, x, sc1, sh1, ACT_SILU, k, s, _dw_wgrad_blocks(Ce)).view_as(Wd)
+                dx, dWe = expand_bwd_z_wide(d1.view(M, Ce), x.view(M, Cin), We_b, consts,
+                                            (rd, rf, H * W) if rd is not None else None, gram, r.expand_bwd)
+            dx, dWe = dx.view(N, H, W, Cin), dWe.view_as(We)
+        elif r.bn1 == "input_bn":
             # the stem BN's backward: statistics from the depthwise epilogue, then apply -> grad of the stem conv output
-            mdz1, mdzx1, dg1, db1 = ext.bn_bwd_finalize_new(pa1, pb1, float(M))
+            mdz1, mdzx1, dg1, db1 = ext.bn_bwd_finalize_new(bn1p[0], bn1p[1], float(M))
             if ctx.stem_link is not None:
                 # the stem's weight-gradient kernel applies this BN backward while staging (StemPreFn.backward)
                 ctx.stem_link.bn = (x, sc1, sh1, mu1, rs1, g1.float().contiguous(), mdz1, mdzx1)
-                dx = dA1.view(N, H, W, Cin)
+                dx = d1.view(N, H, W, Cin)
             else:
-                dx = ext.bn_bwd_apply(dA1, None, None, 0, x, sc1, sh1, mu1, rs1, g1.float().contiguous(), ACT_SILU,
+                dx = ext.bn_bwd_apply(d1, None, None, 0, x, sc1, sh1, mu1, rs1, g1.float().contiguous(), ACT_SILU,
                                       mdz1, mdzx1).view(N, H, W, Cin)
-            dWe = None
         else:
-            if dy2 is not None:
-                (dx,) = ext.dw_bwd_data(dy2, wd, H, W, k, s, None, None, None, None, None, MAX_BLOCKS)
-                dWd = ext.dw_bwd_weight(dy2, x, None, None, ACT_NONE, k, s, _dw_wgrad_blocks(Ce)).view_as(Wd)
-            dg1 = db1 = dWe = None
-        if spec.has_skip and not skip_done:
+            dx = d1
+        if r.residual == "add_scaled":
             ext.add_scaled_(dx.view(N, HW2, Cout), dout.view(N, HW2, Cout), fmul.float().contiguous())
         _mark(f"bwd{spec.index}_end")
         return (dx, dmul, dadd, None, dWe, dg1, db1, dWd, dg2, db2, df1w, df1b, df2w, df2b, dWp, dg3, db3, None)
@@ -1081,8 +1069,8 @@ def encoder_forward(encoder, frames: torch.Tensor, context: Optional[torch.Tenso
     N = frames.shape[0]
     stem = net.convNormAct0
     first = net.blocks[0]
-    stem_into_block0 = STEM_IN_BLOCK0 and first.expand is None and not first.spec.has_skip
-    link = StemLink() if (stem_into_block0 and STEM_BN_BWD_FUSED) else None
+    stem_into_block0 = FLAGS.stem_in_block0 and first.expand is None and not first.spec.has_skip
+    link = StemLink() if (stem_into_block0 and FLAGS.stem_bn_bwd) else None
     if stem_into_block0:
         x, *stem_consts = StemPreFn.apply(frames, shift, stem[0].weight, BNCtx(stem[1]), training, link)
     else:
@@ -1108,11 +1096,11 @@ def encoder_forward(encoder, frames: torch.Tensor, context: Optional[torch.Tenso
         bns = ([BNCtx(e[1])] if e is not None else []) + [BNCtx(dw[1]), BNCtx(pj[1])]
         if i == 0 and stem_into_block0:
             # the stem BN's gamma / beta ride in the (absent) expand BN's slots; its constants in meta
-            g1_, b1_, meta = stem[1].weight, stem[1].bias, (sp, bns, training, tuple(stem_consts), link)
+            g1_, b1_, meta = stem[1].weight, stem[1].bias, BlockMeta(sp, bns, training, tuple(stem_consts), link)
         else:
             g1_ = e[1].weight if e is not None else None
             b1_ = e[1].bias if e is not None else None
-            meta = (sp, bns, training)
+            meta = BlockMeta(sp, bns, training)
         x = MBConvFn.apply(x, fmul, fadd, keep, e[0].weight if e is not None else None, g1_, b1_,
                            dw[0].weight, dw[1].weight, dw[1].bias,
                            se.fc1.weight, se.fc1.bias, se.fc2.weight, se.fc2.bias,

@@ -52,7 +52,7 @@ def test_eager_dp_bitwise_reproducible_with_fused_se():
     bitwise equal for 8 steps, with the fused SE kernels on (the default for any world size).  Before the packed-fp32
     op_sel fix (profiles/r4_se_dp_rootcause.md) single SE fc1 weight gradients differed run to run here."""
     from pytorch_rt1_for_distributed_training_amd.ops import backbone
-    assert backbone.se_fused_active()
+    assert backbone.FLAGS.se_fused
     r = _torchrun([os.path.join(ROOT, "tools", "dp_gpu_check.py"), "--eager2", "--steps", "8"], 29546)
     assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-4000:])
     steps = [ln for ln in r.stdout.splitlines() if ln.startswith("step ")]

@@ -154,13 +154,13 @@ def test_gram_one_pass(ext, C, M, variant, splits):
     torch.testing.assert_close(G, ext.wgrad(x, x, variant=variant, splits=splits), rtol=1e-5, atol=1e-5 * M ** 0.5)
 
 
-def test_mbconv_xmode_vs_stored(ext, monkeypatch):
+def test_mbconv_xmode_vs_stored(ext):
     """MBConvFn of blocks 2-8 with x-mode on and off: same outputs, gradients and running statistics (the only
     difference is fp32 vs bf16-tensor BN1 statistics and MFMA vs library y1 rounding)."""
     import copy
+    import dataclasses
     from pytorch_rt1_for_distributed_training_amd.models.efficientnet import FiLMEfficientNet
-    from pytorch_rt1_for_distributed_training_amd.ops import backbone
-    from pytorch_rt1_for_distributed_training_amd.ops.backbone import BNCtx, MBConvFn
+    from pytorch_rt1_for_distributed_training_amd.ops.backbone import FLAGS, BlockMeta, BNCtx, MBConvFn, plan_block
     torch.manual_seed(0)
     net = FiLMEfficientNet().cuda().train()
     N = 6
@@ -174,16 +174,16 @@ def test_mbconv_xmode_vs_stored(ext, monkeypatch):
         fadd = torch.randn(N, sp.out_ch, device="cuda") * 0.1
         g = None
         outs = []
-        monkeypatch.setattr(backbone, "XMODE_SHAPES", None)           # every supported block
-        for xm in (True, False):
-            monkeypatch.setattr(backbone, "XMODE", xm)
+        for xm in ("all", "0"):                                       # every supported block / none
+            route = plan_block(sp, N, H, W, False, dataclasses.replace(FLAGS, xmode=xm))
+            assert (route.bn1 == "xmode") == (xm == "all"), (i, route)
             b = copy.deepcopy(blk)
             e, dw, se, pj = b.expand, b.depthwise, b.se, b.project
             bns = [BNCtx(e[1]), BNCtx(dw[1]), BNCtx(pj[1])]
             xf = x.clone().requires_grad_(True)
             out = MBConvFn.apply(xf, fmul, fadd, None, e[0].weight, e[1].weight, e[1].bias, dw[0].weight, dw[1].weight,
                                  dw[1].bias, se.fc1.weight, se.fc1.bias, se.fc2.weight, se.fc2.bias, pj[0].weight,
-                                 pj[1].weight, pj[1].bias, (sp, bns, True))
+                                 pj[1].weight, pj[1].bias, BlockMeta(sp, bns, True, route=route))
             if g is None:
                 g = torch.randn_like(out.float()).to(BF)
             grads = torch.autograd.grad(out, [xf, e[0].weight, e[1].weight, e[1].bias, dw[0].weight, pj[0].weight], g)

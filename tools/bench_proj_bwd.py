@@ -44,9 +44,10 @@ def main():
     tot_o = tot_n = 0.0
     for sp in block_specs():
         Ho, Wo = conv_out_size(H, sp.kernel, sp.stride), conv_out_size(W, sp.kernel, sp.stride)
+        prologue = backbone.plan_block(sp, N, H, W, False).proj_fwd == "pw_gemm"
         H, W = Ho, Wo
         Ce, Cout, HW = sp.expand_ch, sp.out_ch, Ho * Wo
-        if not ext.proj_bwd_supported(Cout, Ce) or not backbone.project_fused(Ce, Cout, HW):
+        if not ext.proj_bwd_supported(Cout, Ce) or not prologue:
             continue
         M = N * HW
         dy3 = (torch.randn(M, Cout, device="cuda") * 0.1).to(torch.bfloat16)

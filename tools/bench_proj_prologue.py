@@ -51,8 +51,8 @@ def main():
         gate = torch.rand(N, Ce, device=dev)
         A = ext.bn_apply(y2, sc, sh, ACT_SILU, gate, HW2)
         t_apply = timeit(lambda: ext.bn_apply(y2, sc, sh, ACT_SILU, gate, HW2), a.iters)
-        if (Ce, Co) in backbone.GEMM_PROJ:
-            kind, cfg = "gemm.hip", backbone.GEMM_PROJ[(Ce, Co)]
+        if (Ce, Co) in backbone.FLAGS.gemm_proj_cfg:
+            kind, cfg = "gemm.hip", backbone.FLAGS.gemm_proj_cfg[(Ce, Co)]
             plain = lambda: ext.gemm(A, wp, False, None, stats=True, cfg=cfg)
             pro = lambda: ext.gemm(y2, wp, False, None, sc, sh, gate, HW2, stats=True, cfg=cfg)
         elif ext.pw_tall_preferred(Ce, Co):

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Project-conv operand prologue (pw_gemm with scale/shift/gate, ops/backbone.py project_fused) vs bn_apply + pw_gemm,
+"""Project-conv operand prologue (pw_gemm with scale/shift/gate, ops/backbone.py plan_block's "pw_gemm") vs bn_apply + pw_gemm,
 at the real RT-1 shapes of the skinny-GEMM blocks, forward (GEMM + BN3 stats) and backward weight gradient
 (wgrad with the same prologue vs wgrad on the materialised A).
 
