@@ -20,11 +20,15 @@
 // registers).  Workgroups loop over tiles (grid <= ~8/CU) so the partial rows
 // stay few and are reduced by bn_finalize.
 #include <algorithm>
+#include <array>
 #include <cstdlib>
+#include <unordered_map>
 
 #include "common.h"
+#include "dw/dw_plan.h"
 
 using namespace rt1;
+using namespace rt1::dw;
 
 namespace {
 
@@ -832,14 +836,8 @@ struct DyBnBwd {   // dy = k1 * (dA * gate + rb) * silu'(y*scale + shift) + k2 *
     const float *scale, *shift, *mean, *rstd, *gamma, *mdz, *mdzx;   // [C]
 };
 
-// stage_tile for dy: each thread owns one channel vector (its 48 constants in registers, folded per frame:
-// a = k1*gate, b = k1*rb) and keeps SU pixels (2 x 16 B each) in flight
 constexpr int DWF_SU = 4;     // pixels (2 x 16-B loads each) in flight per thread while staging dy
 constexpr int DWF_OCC = 2;    // workgroups / CU the fused kernel's register budget targets
-constexpr int STAGE_V2 = 1;   // buffer-load + packed-math staging (stage_dy_v2); 0 = the branchy per-pixel version
-#ifndef DW_STAGE_PHASED
-#define DW_STAGE_PHASED 1
-#endif
 #ifndef DW_CENTRE_PREFETCH
 #define DW_CENTRE_PREFETCH 1
 #endif
@@ -871,12 +869,14 @@ __device__ __forceinline__ uint4 buf_load16(__amdgpu_buffer_rsrc_t r, uint32_t o
     return make_uint4(v.x, v.y, v.z, v.w);
 }
 
-// stage_dy with every pixel's two 16-B loads issued unconditionally through buffer descriptors (offset OOB for halo
-// pixels and idle channel lanes -> zeros) and the per-element math in packed f32 (two channels per instruction):
-// ~half the VALU issue of the branchy version per element.
+// stage_tile for dy: each thread owns one channel vector (its 48 constants in registers, folded per frame:
+// a = k1*gate, b = k1*rb) and keeps SU pixels (2 x 16 B each) in flight.  Every pixel's two 16-B loads are issued
+// unconditionally through buffer descriptors (offset OOB for halo pixels and idle channel lanes -> zeros) and the
+// per-element math is packed f32 (two channels per instruction): ~half the VALU issue per element of per-pixel
+// branches around scalar math.
 template <int SU, bool RING>
-__device__ __forceinline__ void stage_dy_v2(uint4* tile, const DyBnBwd& d, const DwGeo& g, int n, int ih0, int iw0,
-                                            int IH, int IW, int v0, int ncv) {
+__device__ __forceinline__ void stage_dy(uint4* tile, const DyBnBwd& d, const DwGeo& g, int n, int ih0, int iw0,
+                                         int IH, int IW, int v0, int ncv) {
     const int cv = g.cv;
     const int t = threadIdx.x;
     const int vv = t % cv, PLs = BLOCK / cv;
@@ -943,7 +943,6 @@ __device__ __forceinline__ void stage_dy_v2(uint4* tile, const DyBnBwd& d, const
             unpack4x2(ug[k], gv);
             unpack4x2(uy[k], yv);
             f2 o[4];
-#if DW_STAGE_PHASED
             // the four channel pairs' dependency chains advanced step by step, so every packed op has three
             // independent ones between it and its producer (one at a time, dependent packed-fp32 ops back to back
             // cost an s_nop each: 67 per 4-pixel staging round in the k3 unified backward)
@@ -971,18 +970,6 @@ __device__ __forceinline__ void stage_dy_v2(uint4* tile, const DyBnBwd& d, const
             for (int j = 0; j < 4; ++j) z[j] = t[j] * z[j];                                                   // silu'(z)
 #pragma unroll
             for (int j = 0; j < 4; ++j) o[j] = z[j] * gv[j] + lin[j];
-#else
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const f2 z = yv[j] * SC[j] + SH[j];
-                const f2 e = z * f2{-1.4426950408889634f, -1.4426950408889634f};   // -z log2 e
-                const f2 one = f2{1.f, 1.f};
-                const f2 q = f2{__builtin_amdgcn_exp2f(e.x), __builtin_amdgcn_exp2f(e.y)} + one;
-                const f2 s = f2{__builtin_amdgcn_rcpf(q.x), __builtin_amdgcn_rcpf(q.y)};
-                const f2 sg = s * (z * (one - s) + one);
-                o[j] = sg * (A[j] * gv[j] + B[j]) + (K2[j] * yv[j] + K0[j]);
-            }
-#endif
             uint4 v = make_uint4(pack2(o[0].x, o[0].y), pack2(o[1].x, o[1].y), pack2(o[2].x, o[2].y),
                                  pack2(o[3].x, o[3].y));
             if (!ok[k]) v = make_uint4(0, 0, 0, 0);
@@ -991,12 +978,12 @@ __device__ __forceinline__ void stage_dy_v2(uint4* tile, const DyBnBwd& d, const
     }
 }
 
-// stage_dy_v2 over HALF vectors (4 channels, 8-byte loads / stores): the per-channel constants of 4 channels (24
+// stage_dy over HALF vectors (4 channels, 8-byte loads / stores): the per-channel constants of 4 channels (24
 // VGPRs instead of 48) and 8-byte loads in flight -- the staging of the 2-channel k5 unified backward, whose K x K
 // weight-gradient accumulators stay live across it (the 8-channel staging pushed it past 168 VGPRs, 3 workgroups/CU)
 template <int SU, bool RING>
-__device__ __forceinline__ void stage_dy_v2h(uint4* tile, const DyBnBwd& d, const DwGeo& g, int n, int ih0, int iw0,
-                                             int IH, int IW, int v0, int ncv) {
+__device__ __forceinline__ void stage_dy_half(uint4* tile, const DyBnBwd& d, const DwGeo& g, int n, int ih0, int iw0,
+                                              int IH, int IW, int v0, int ncv) {
     const int cv = g.cv, ch = 2 * cv;
     const int t = threadIdx.x;
     const int hv = t % ch, PLs = BLOCK / ch;
@@ -1056,7 +1043,6 @@ __device__ __forceinline__ void stage_dy_v2h(uint4* tile, const DyBnBwd& d, cons
             col += dc;
             if (col >= qw) { col -= qw; ++row; }
         }
-#if DW_STAGE_PHASED
         // the SU pixels' two channel pairs advanced phase by phase (8 independent packed chains; pair by pair the
         // dependent packed ops each cost an s_nop)
         f2 o[SU][2];
@@ -1118,102 +1104,8 @@ __device__ __forceinline__ void stage_dy_v2h(uint4* tile, const DyBnBwd& d, cons
             const int p = RING ? px[k] : pb + k * PLs;
             if (pb + k * PLs >= npix) break;
             uint2 v = make_uint2(pack2(o[k][0].x, o[k][0].y), pack2(o[k][1].x, o[k][1].y));
-#else
-#pragma unroll
-        for (int k = 0; k < SU; ++k) {
-            const int p = RING ? px[k] : pb + k * PLs;
-            if (pb + k * PLs >= npix) break;
-            const f2 gv[2] = {f2{__uint_as_float(ug[k].x << 16), __uint_as_float(ug[k].x & 0xffff0000u)},
-                              f2{__uint_as_float(ug[k].y << 16), __uint_as_float(ug[k].y & 0xffff0000u)}};
-            const f2 yv[2] = {f2{__uint_as_float(uy[k].x << 16), __uint_as_float(uy[k].x & 0xffff0000u)},
-                              f2{__uint_as_float(uy[k].y << 16), __uint_as_float(uy[k].y & 0xffff0000u)}};
-            f2 o[2];
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const f2 z = yv[j] * SC[j] + SH[j];
-                const f2 e = z * f2{-1.4426950408889634f, -1.4426950408889634f};
-                const f2 one = f2{1.f, 1.f};
-                const f2 q = f2{__builtin_amdgcn_exp2f(e.x), __builtin_amdgcn_exp2f(e.y)} + one;
-                const f2 s = f2{__builtin_amdgcn_rcpf(q.x), __builtin_amdgcn_rcpf(q.y)};
-                const f2 sg = s * (z * (one - s) + one);
-                o[j] = sg * (A[j] * gv[j] + B[j]) + (K2[j] * yv[j] + K0[j]);
-            }
-            uint2 v = make_uint2(pack2(o[0].x, o[0].y), pack2(o[1].x, o[1].y));
-#endif
             if (!ok[k]) v = make_uint2(0, 0);
             tl[p * ch + hv] = v;
-        }
-    }
-}
-
-template <int SU = DWF_SU, bool RING = false>
-__device__ __forceinline__ void stage_dy(uint4* tile, const DyBnBwd& d, const DwGeo& g, int n, int ih0, int iw0, int IH,
-                                         int IW, int v0, int ncv) {
-    if constexpr (STAGE_V2) {
-        stage_dy_v2<SU, RING>(tile, d, g, n, ih0, iw0, IH, IW, v0, ncv);
-        return;
-    }
-    const int cv = g.cv;
-    const int t = threadIdx.x;
-    const int vv = t % cv, PLs = BLOCK / cv;
-    int pb = t / cv;
-    if (pb >= PLs) return;
-    const bool cvalid = vv < ncv;
-    const int c0 = (v0 + (cvalid ? vv : 0)) * 8;
-    float a[8], b[8], k2[8], k0[8], sc[8], sh[8];
-    {
-        float gm[8], rr[8], mu[8], mz[8], mx[8];
-        load8f(d.gamma + c0, gm); load8f(d.rstd + c0, rr); load8f(d.mean + c0, mu);
-        load8f(d.mdz + c0, mz); load8f(d.mdzx + c0, mx);
-        load8f(d.gate + (int64_t)n * g.C + c0, a); load8f(d.rb + (int64_t)n * g.C + c0, b);
-        load8f(d.scale + c0, sc); load8f(d.shift + c0, sh);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float k1 = gm[j] * rr[j];
-            k2[j] = -k1 * rr[j] * mx[j];
-            k0[j] = -k1 * (mz[j] - mu[j] * rr[j] * mx[j]);
-            a[j] *= k1;
-            b[j] *= k1;
-        }
-    }
-    const int64_t fb = (int64_t)n * g.H * g.W * g.C + c0;
-    const bf16_t* gb = d.dA + fb;
-    const bf16_t* yb = d.y + fb;
-    const int npix = IH * IW;
-    int row = pb / IW, col = pb - row * IW;
-    const int dr = PLs / IW, dc = PLs - dr * IW;
-    for (; pb < npix; pb += PLs * SU) {
-        uint4 ug[SU], uy[SU];
-        unsigned valid = 0;
-#pragma unroll
-        for (int k = 0; k < SU; ++k) {
-            const int ih = ih0 + row, iw = iw0 + col;
-            ug[k] = uy[k] = make_uint4(0, 0, 0, 0);
-            if (cvalid && pb + k * PLs < npix && (unsigned)ih < (unsigned)g.H && (unsigned)iw < (unsigned)g.W) {
-                const uint32_t off = (uint32_t)(ih * g.W + iw) * (uint32_t)g.C;
-                ug[k] = *reinterpret_cast<const uint4*>(gb + off);
-                uy[k] = *reinterpret_cast<const uint4*>(yb + off);
-                valid |= 1u << k;
-            }
-            row += dr;
-            col += dc;
-            if (col >= IW) { col -= IW; ++row; }
-        }
-#pragma unroll
-        for (int k = 0; k < SU; ++k) {
-            const int p = pb + k * PLs;
-            if (p >= npix) break;
-            uint4 v = make_uint4(0, 0, 0, 0);
-            if (valid >> k & 1u) {
-                float gv[8], yv[8], o[8];
-                unpack8(ug[k], gv);
-                unpack8(uy[k], yv);
-#pragma unroll
-                for (int j = 0; j < 8; ++j)
-                    o[j] = fmaf(silu_grad(fmaf(yv[j], sc[j], sh[j])), fmaf(a[j], gv[j], b[j]), fmaf(k2[j], yv[j], k0[j]));
-                v.x = pack2(o[0], o[1]); v.y = pack2(o[2], o[3]); v.z = pack2(o[4], o[5]); v.w = pack2(o[6], o[7]);
-            }
-            tile[p * cv + vv] = v;
         }
     }
 }
@@ -1268,7 +1160,7 @@ __global__ __launch_bounds__(BLOCK, DWF_OCC) void dw_bwd_fused_kernel(DyBnBwd d,
         const int rem = (int)(tile_id - (int64_t)n * tiles_h * tiles_w);
         const int oh0 = (rem / tiles_w) * TH, ow0 = (rem % tiles_w) * TW;
         __syncthreads();
-        stage_dy(dt, d, g, n, oh0 - P, ow0 - P, IH, IW, v0, ncv);
+        stage_dy<DWF_SU, false>(dt, d, g, n, oh0 - P, ow0 - P, IH, IW, v0, ncv);
         stage_tile(at, x1, g, n, oh0 - P, ow0 - P, IH, IW, g.H, g.W, v0, ncv, scale1, shift1, act1);
         __syncthreads();
         if (lane_cv >= ncv) continue;
@@ -1438,7 +1330,7 @@ __device__ __forceinline__ void pin(f2& v) { asm volatile("" : "+v"(v)); }
 // Strip centres' BN1 + SiLU for the unified backward kernels: z = y * sc + sh, a = silu(z) (zero where !ok: no weight
 // contribution past the right edge), gp = silu'(z) = s (1 + z (1 - s)).  Written phase by phase over all R x NV channel
 // pairs so that each packed op has independent ones between it and its producer: computed pair by pair, the chain's
-// back-to-back dependent packed-fp32 ops each cost an s_nop (DW_STAGE_PHASED).
+// back-to-back dependent packed-fp32 ops each cost an s_nop (as in stage_dy; profiles/r6_dw_phased_ab.log).
 template <int R, int NV>
 __device__ __forceinline__ void centre_silu(const f2 (&y)[R][NV], const f2 (&sc)[NV], const f2 (&sh)[NV],
                                             const bool (&ok)[R], f2 (&a)[R][NV], f2 (&gp)[R][NV]) {
@@ -1552,7 +1444,7 @@ __global__ __launch_bounds__(BLOCK, CPT == 2 ? DWU2_OCC : DWU_OCC) void dw_bwd_u
             }
         }
 #if !(RT1_DW_TIMING & 2)   // timing-only build (tools/bench_dw_phases.py): no dy staging
-        if constexpr (CPT == 2) stage_dy_v2h<DWU2_SU, RG>(dt, d, g, n, oh0 - P, ow0 - P, IH, IW, v0, ncv);
+        if constexpr (CPT == 2) stage_dy_half<DWU2_SU, RG>(dt, d, g, n, oh0 - P, ow0 - P, IH, IW, v0, ncv);
         else stage_dy<DWU_SU, RG>(dt, d, g, n, oh0 - P, ow0 - P, IH, IW, v0, ncv);
 #endif
         if constexpr (CS) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the centre DMA has landed
@@ -1631,7 +1523,6 @@ __global__ __launch_bounds__(BLOCK, CPT == 2 ? DWU2_OCC : DWU_OCC) void dw_bwd_u
                 f2 sc[NV], sh[NV];
                 CV::loadf(ecl + co, sc);
                 CV::loadf(ecl + C8 + co, sh);
-#if DW_STAGE_PHASED
                 f2 y[R][NV];
                 bool ok[R];
 #pragma unroll
@@ -1640,22 +1531,6 @@ __global__ __launch_bounds__(BLOCK, CPT == 2 ? DWU2_OCC : DWU_OCC) void dw_bwd_u
                     ok[r] = ow0 + tx + r < g.W;
                 }
                 centre_silu<R, NV>(y, sc, sh, ok, a, gp);
-#else
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    f2 y[NV];
-                    CV::unpack(yr[r], y);
-                    const bool ok = ow0 + tx + r < g.W;
-#pragma unroll
-                    for (int j = 0; j < NV; ++j) {
-                        const f2 z = y[j] * sc[j] + sh[j];
-                        const f2 s = f2{sigmoidf_(z.x), sigmoidf_(z.y)};
-                        const f2 one = f2{1.f, 1.f};
-                        a[r][j] = ok ? z * s : f2{0.f, 0.f};
-                        gp[r][j] = s * (z * (one - s) + one);       // silu'(z)
-                    }
-                }
-#endif
             } else {
 #pragma unroll
                 for (int r = 0; r < R; ++r) CV::unpack(yr[r], a[r]);
@@ -1854,7 +1729,6 @@ __device__ __forceinline__ void uni_s2_class(const uint4* __restrict__ dt, const
             f2 sc[NV], sh[NV];
             CV::loadf(ecl + co, sc);
             CV::loadf(ecl + C8 + co, sh);
-#if DW_STAGE_PHASED
             f2 y[R][NV];
             bool ok[R];
 #pragma unroll
@@ -1863,22 +1737,6 @@ __device__ __forceinline__ void uni_s2_class(const uint4* __restrict__ dt, const
                 ok[r] = iwb + 2 * r < g.W;
             }
             centre_silu<R, NV>(y, sc, sh, ok, a, gp);
-#else
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                f2 y[NV];
-                CV::unpack(yr[r], y);
-                const bool ok = iwb + 2 * r < g.W;
-#pragma unroll
-                for (int j = 0; j < NV; ++j) {
-                    const f2 z = y[j] * sc[j] + sh[j];
-                    const f2 s = f2{sigmoidf_(z.x), sigmoidf_(z.y)};
-                    const f2 one = f2{1.f, 1.f};
-                    a[r][j] = ok ? z * s : f2{0.f, 0.f};
-                    gp[r][j] = s * (z * (one - s) + one);
-                }
-            }
-#endif
         } else {
 #pragma unroll
             for (int r = 0; r < R; ++r) CV::unpack(yr[r], a[r]);
@@ -2085,6 +1943,7 @@ __global__ __launch_bounds__(BLOCK, DWU_OCC) void dw_bwd_uni_s2_kernel(DyBnBwd d
     }
 }
 
+// ================================================================== launch plan (dw/dw_plan.h)
 DwGeo make_geo(int N, int H, int W, int C, int k, int s) {
     DwGeo g;
     g.N = N; g.H = H; g.W = W; g.C = C; g.k = k; g.s = s; g.pad = (k - 1) / 2;
@@ -2128,6 +1987,14 @@ int xk_of(int cin, int C, int k, int s) {
     return kc * 16 + ng;
 }
 
+// is (k, xk) one of the compiled x-mode specialisations of this stride
+bool x_supported(int k, int s, int xk) {
+#define X(KK, XX) if (k == KK && xk == XX) return true;
+    if (s == 1) { DW_XMODE_S1(X) } else { DW_XMODE_S2(X) }
+#undef X
+    return false;
+}
+
 // ---------------------------------------------------------------- tile selection
 // A workgroup's 256 threads form `slots` strip lanes; a tile of G strips takes ceil(G / slots) rounds,
 // so a tile shape that leaves the last round mostly idle (35 strips on 32 lanes) costs nearly 2x.
@@ -2135,21 +2002,8 @@ int xk_of(int cin, int C, int k, int s) {
 // shapes that fit the LDS budget (3 workgroups/CU):
 //   cost = tiles * (ceil(strips / slots) * strip_cost + ceil(staged vectors / 256) * stage_cost + sync)
 // strip/stage costs are VALU instruction counts read off the gfx950 ISA of each kernel.
-enum TileKind : int {
-    TK_FWD = 0, TK_BWD_W = 1, TK_BWD_S2 = 2, TK_BWD_F = 3, TK_BWD_U4 = 4, TK_BWD_U8 = 5, TK_BWD_V4 = 6, TK_BWD_V8 = 7,
-    TK_BWD_U2 = 8
-};   // U: unified stride-1 backward, V: unified stride-2 backward (2 / 4 / 8 channels per thread)
-// unified backward (dw_bwd_uni_kernel): channels per thread and strip length per kernel size
-constexpr int DWU_CPT3 = 8;
-constexpr int DWU_R3 = 2;
-constexpr int DWU_CPT5 = 4;
-constexpr int DWU_R5 = 4;
 constexpr int DW_R5_MASK = 1;   // profiles/r3_dw_r5_ab.log: forward +0.3 %; the k5 unified backward at R=5 spills 69 VGPRs, -1.6 %
 constexpr int DWU_LDS_KB = 76;     // unified backward: one staged dy tile, 2 workgroups / CU
-constexpr int DWV_CPT3 = 8;
-constexpr int DWV_R3 = 2;
-constexpr int DWV_CPT5 = 4;
-constexpr int DWV_R5 = 4;
 // The k5 unified backward (y1 in HBM, not x-mode) with 2 channels per thread -- 50 weight-gradient
 // accumulators instead of 100, so DWU2_OCC workgroups / CU fit (tiles within DWU2_LDS_KB of LDS)
 constexpr int DWU2_LDS_KB = 52;
@@ -2160,13 +2014,13 @@ inline int uni_kind(int K, int xk, int H, int W) {
     if (K == 5 && xk == 0 && H * W <= DWU2_MAX_PIX) return TK_BWD_U2;
     return (K == 3 ? DWU_CPT3 : DWU_CPT5) == 4 ? TK_BWD_U4 : TK_BWD_U8;
 }
-inline bool is_uni(int kind) { return kind == TK_BWD_U4 || kind == TK_BWD_U8 || kind == TK_BWD_U2; }
+inline bool is_uni2(int kind) { return kind == TK_BWD_V4 || kind == TK_BWD_V8; }
 // 5-output strips on maps whose width is a multiple of 5 but not of 4 (150, 75, 10): the strips then tile the row
 // exactly (10x10: no third of a 12-wide tile idles) and each staged input vector feeds one more output.
 // DW_R5_MASK: 1 = forward / stride-1 data-gradient kernels, 2 = unified k5 backward.  x-mode kernels keep their one
 // strip length.
 inline bool r5_fits(int W, int xk, int bit) { return xk == 0 && W > 0 && W % 5 == 0 && W % 4 != 0 && (DW_R5_MASK & bit); }
-inline int uni_r(int K, int W = 0, int xk = 0, int cpt = 0) {
+inline int uni_r(int K, int W, int xk, int cpt) {
     // the 2-channel form has the registers for 5-output strips on the 10-wide maps (no idle third of a 12-wide tile)
     if (K == 5 && cpt == 2 && xk == 0 && W > 0 && W % 5 == 0 && W % 4 != 0) return 5;
     return K == 3 ? DWU_R3 : (r5_fits(W, xk, 2) ? 5 : DWU_R5);
@@ -2178,16 +2032,10 @@ inline int kind_cpt(int kind) {
 }
 // variant: 0 = two-pass fused kernel, 1 = unified kernel, -1 = per-layer default.  The unified kernel builds its
 // operand as BN1 + SiLU exactly when the BN1 epilogue is on (expand blocks) and uses x1 raw otherwise.
-}  // namespace
-
-extern "C" int rt1_dw_bwd_uses_uni(int variant, int pro, int epi);
-
-namespace {
 inline bool use_uni(int variant, bool pro, bool epi) {
     if (pro != epi) return false;
     return variant != 0;
 }
-constexpr int DW_R1 = 4;      // outputs per thread strip for the stride-1 forward / weight-grad kernels
 inline int fwd_r(int S, int Wo, int xk) { return S == 1 && r5_fits(Wo, xk, 1) ? 5 : DW_R1; }
 struct TileChoice { int TH, TW, sb = 0; };   // sb: x-mode stride-1 backward strips per band (0 = all)
 
@@ -2195,14 +2043,12 @@ constexpr int DW_LDS_KB = 52;      // LDS per workgroup the tile search may use 
 constexpr size_t LDS_BUDGET = DW_LDS_KB * 1024;
 constexpr int DWF_LDS_KB = 76;     // fused backward: two staged tiles, 2 workgroups / CU
 
-// xk != 0 (x-mode): the forward adds BN1's staged constants, the unified backward kernels the y1 centre buffer
-// (stride 1: a band of bh rows x TW; stride 2: one parity class, TH/2 x TW/2) and the We image
-size_t tile_lds(int kind, int K, int S, int cv, bool epi, int TH, int TW, int xk = 0, int sb = 0, int mapw = 0) {
+// R: the strip length of the request (unified kernels only).  xk != 0 (x-mode): the forward adds BN1's staged
+// constants, the unified backward kernels the y1 centre buffer (stride 1: a band of sb strips, or the whole tile;
+// stride 2: one parity class, TH/2 x TW/2) and the We image
+size_t tile_lds(int kind, int K, int S, int cv, bool epi, int R, int TH, int TW, int xk, int sb) {
     const size_t ec = epi ? (size_t)cv * 8 * 4 * 4 : 0;
-    // sb > 0 only in x-mode, whose strips keep the default length
-    const int R = is_uni(kind) ? uni_r(K) : 1;
-    const size_t ypix = (kind == TK_BWD_V4 || kind == TK_BWD_V8) ? (size_t)(TH / 2) * (TW / 2)
-                                                                 : (sb > 0 ? (size_t)sb * R : (size_t)TH * TW);
+    const size_t ypix = is_uni2(kind) ? (size_t)(TH / 2) * (TW / 2) : (sb > 0 ? (size_t)sb * R : (size_t)TH * TW);
     const size_t xt = xk ? ypix * cv * 16 + (size_t)cv * 8 * ((xk >> 4) * 32 + 8) * 2 : 0;
     if (kind == TK_FWD) {
         const int IH = (TH - 1) * S + K, IW = (TW - 1) * S + K;
@@ -2216,7 +2062,7 @@ size_t tile_lds(int kind, int K, int S, int cv, bool epi, int TH, int TW, int xk
         const size_t red = (size_t)(BLOCK / (cv * K)) * cv * 8 * K * K * 4;
         return a > red ? a : red;
     }
-    if (kind == TK_BWD_V4 || kind == TK_BWD_V8) {
+    if (is_uni2(kind)) {
         const int DH = (TH + K) / 2 + 1, DW = (TW + K) / 2 + 1, cpt = kind_cpt(kind);
         const size_t a = (size_t)DH * DW * cv * 16 + (size_t)K * K * cv * 8 * 4 + ec + xt;
         const size_t red = (size_t)(BLOCK / (cv * 8 / cpt)) * cv * 8 * 2 * 4;
@@ -2224,7 +2070,7 @@ size_t tile_lds(int kind, int K, int S, int cv, bool epi, int TH, int TW, int xk
     }
     if (is_uni(kind)) {
         const int IH = TH + K - 1, IW = TW + K - 1, cpt = kind_cpt(kind);
-        const size_t cs = (!xk && centre_stage_on(cpt, uni_r(K, mapw, xk, cpt))) ? (size_t)TH * TW * cv * 16 : 0;
+        const size_t cs = (!xk && centre_stage_on(cpt, R)) ? (size_t)TH * TW * cv * 16 : 0;
         const size_t a = (size_t)IH * IW * cv * 16 + (size_t)K * K * cv * 8 * 4 + ec + xt + cs;
         const size_t red = (size_t)(BLOCK / (cv * 8 / cpt)) * cv * 8 * 2 * 4;   // 2 rows of partials (>= 1 tap)
         return a > red ? a : red;
@@ -2242,11 +2088,10 @@ size_t tile_lds(int kind, int K, int S, int cv, bool epi, int TH, int TW, int xk
     return a > red ? a : red;
 }
 
-TileChoice search_tile(int kind, int Ho, int Wo, int K, int S, int cv, bool pro, bool epi, int xk) {
+// the cheapest tile of a Ho x Wo map for strips of R outputs
+TileChoice search_tile(int kind, int R, int Ho, int Wo, int K, int S, int cv, bool pro, bool epi, int xk) {
     const bool uni = is_uni(kind);
-    const bool uni2 = kind == TK_BWD_V4 || kind == TK_BWD_V8;
-    const int R = uni2 ? uni2_r(K) : uni ? uni_r(K, Wo, xk, kind_cpt(kind)) : kind == TK_BWD_S2 ? 4
-                : kind == TK_FWD ? (S == 1 ? fwd_r(S, Wo, xk) : 2) : (S == 1 ? DW_R1 : 2);
+    const bool uni2 = is_uni2(kind);
     const int NIN = (R - 1) * S + K;
     const int wstep = kind == TK_BWD_S2 ? 8 : uni2 ? 2 * R : R, hstep = (kind == TK_BWD_S2 || uni2) ? 2 : 1;
     int slots, strip;
@@ -2294,7 +2139,7 @@ TileChoice search_tile(int kind, int Ho, int Wo, int K, int S, int cv, bool pro,
             const int all = TH * (TW / R);
             const int sbv = nr > 0 ? nr * slots : 0;
             if (nr > 0 && sbv >= all) continue;
-            if (tile_lds(kind, K, S, cv, epi, TH, TW, xk, sbv, Wo) > budget) continue;
+            if (tile_lds(kind, K, S, cv, epi, R, TH, TW, xk, sbv) > budget) continue;
             fits_any = true;
             const int nb = sbv > 0 ? cdiv(all, sbv) : 1;
             const int tiles = cdiv(Ho, TH) * cdiv(Wo, TW);
@@ -2331,24 +2176,6 @@ TileChoice search_tile(int kind, int Ho, int Wo, int K, int S, int cv, bool pro,
     return best;
 }
 
-// per-thread cache: the search runs once per (layer shape, kernel) and the launch path stays O(1)
-TileChoice pick_tile(int kind, int Ho, int Wo, int K, int S, int cv, bool pro, bool epi, int xk = 0) {
-    struct Entry { int key[8]; TileChoice t; };
-    thread_local Entry cache[64];
-    thread_local int used = 0;
-    const int key[8] = {kind | (xk << 8), Ho, Wo, K, S, cv, pro ? 1 : 0, epi ? 1 : 0};
-    for (int i = 0; i < used; ++i) {
-        bool eq = true;
-        for (int j = 0; j < 8; ++j) eq = eq && cache[i].key[j] == key[j];
-        if (eq) return cache[i].t;
-    }
-    const TileChoice t = search_tile(kind, Ho, Wo, K, S, cv, pro, epi, xk);
-    Entry& e = cache[used < 64 ? used++ : (Ho * 31 + Wo + K) & 63];
-    for (int j = 0; j < 8; ++j) e.key[j] = key[j];
-    e.t = t;
-    return t;
-}
-
 int clamp_grid(int64_t tiles, int max_blocks_x) {
     int64_t gx = tiles < max_blocks_x ? tiles : max_blocks_x;
     return (int)(gx < 1 ? 1 : gx);
@@ -2366,85 +2193,218 @@ int chunk_cap(int max_blocks_x, int chunks) {
     return cap < max_blocks_x ? cap : max_blocks_x;
 }
 
+// Everything of a plan but the frame count and the grid (which only scale with N): one frame's plan.  `tiles` =
+// tiles per frame.
+DwPlan plan_frame(int op, int H, int W, int C, int k, int s, bool pro, bool epi, bool unified, int cin, int& tiles) {
+    if (op == OP_BWD_FUSED_S1) s = 1;
+    if (op == OP_BWD_FUSED_S2) s = 2;
+    const DwGeo g = make_geo(1, H, W, C, k, s);
+    DwPlan p{};
+    p.N = 1; p.H = H; p.W = W; p.C = C; p.Ho = g.Ho; p.Wo = g.Wo; p.k = k; p.s = s; p.pad = g.pad;
+    p.nv = g.nv; p.cv = g.cv; p.chunks = g.chunks;
+    p.cpt = 8;
+    bool ok = (k == 3 || k == 5) && (s == 1 || s == 2);
+    int mh = g.Ho, mw = g.Wo, S = s;      // the tiled map and the stride of the tile search
+    switch (op) {
+    case OP_FWD_X:
+        p.xk = xk_of(cin, C, k, s);
+        ok = ok && x_supported(k, s, p.xk);
+        [[fallthrough]];
+    case OP_FWD:
+        p.kind = TK_FWD;
+        p.R = s == 1 ? fwd_r(s, g.Wo, p.xk) : 2;
+        p.ring = op == OP_FWD && H * W <= DW_RING_PIX;
+        break;
+    case OP_BWD_DATA:          // grid over the INPUT space (the backward output)
+        mh = H; mw = W; pro = false;
+        if (s == 1) {          // as a forward over dy (H == Ho) with flipped taps
+            p.kind = TK_FWD;
+            p.R = fwd_r(1, W, 0);
+            p.ring = g.Ho * g.Wo <= DW_RING_PIX;
+        } else {
+            p.kind = TK_BWD_S2;
+            p.R = 4;
+            S = 2;
+        }
+        break;
+    case OP_BWD_WEIGHT:
+        p.kind = TK_BWD_W;
+        p.R = s == 1 ? DW_R1 : 2;
+        epi = false;
+        break;
+    case OP_BWD_FUSED_S1: {    // grid over the H x W map
+        mh = H; mw = W;
+        const bool uni = use_uni(unified ? 1 : 0, pro, epi);
+        p.xk = (cin > 0 && uni) ? xk_of(cin, C, k, 1) : 0;
+        p.kind = uni ? uni_kind(k, p.xk, H, W) : TK_BWD_F;
+        p.cpt = kind_cpt(p.kind);
+        p.R = uni ? uni_r(k, W, p.xk, p.cpt) : DW_R1;
+        p.ring = uni && H * W <= DW_RING_PIX;
+        // x-mode (y1 recomputed from the block input): unified kernel with the BN1 epilogue only
+        if (cin > 0) ok = ok && uni && epi && x_supported(k, 1, p.xk);
+        break;
+    }
+    case OP_BWD_FUSED_S2:      // grid over the INPUT map (the dx / centre space)
+        mh = H; mw = W; pro = epi;
+        p.xk = cin > 0 ? xk_of(cin, C, k, 2) : 0;
+        p.kind = uni2_kind(k);
+        p.cpt = kind_cpt(p.kind);
+        p.R = uni2_r(k);
+        p.ring = g.Ho * g.Wo <= DW_RING_PIX;   // the staged dy map
+        if (cin > 0) ok = ok && epi && x_supported(k, 2, p.xk);
+        break;
+    default:
+        ok = false;
+        p.kind = TK_FWD;
+        p.R = DW_R1;
+    }
+    const TileChoice tc = search_tile(p.kind, p.R, mh, mw, k, S, g.cv, pro, epi, p.xk);
+    p.TH = tc.TH; p.TW = tc.TW; p.sb = tc.sb;
+    if (op == OP_BWD_FUSED_S2 && ((tc.TH & 1) || (tc.TW % (2 * p.R)))) ok = false;
+    p.lds = (int)tile_lds(p.kind, k, S, g.cv, epi, p.R, tc.TH, tc.TW, p.xk, tc.sb);
+    if (is_uni(p.kind) || is_uni2(p.kind)) {
+        const size_t per_tap = (size_t)(BLOCK / (g.cv * 8 / p.cpt)) * g.cv * 8 * 4;
+        p.red_taps = (int)std::min<size_t>((size_t)k * k, (size_t)p.lds / per_tap);
+    }
+    tiles = cdiv(mh, tc.TH) * cdiv(mw, tc.TW);
+    p.err = ok ? 0 : (int)hipErrorInvalidValue;
+    return p;
+}
+
+}  // namespace
+
+namespace rt1 {
+namespace dw {
+
+DwPlan dw_plan(int op, int N, int H, int W, int C, int k, int s, int pro, int epi, int variant, int cin,
+               int max_blocks_x) {
+    // per-thread memo keyed on the whole request but N / max_blocks_x: the tile search runs once per key and the
+    // launch path stays O(1)
+    typedef std::array<int, 10> Key;
+    struct Hash {
+        size_t operator()(const Key& a) const {
+            size_t h = 1469598103934665603ull;
+            for (int v : a) h = (h ^ (size_t)(unsigned)v) * 1099511628211ull;
+            return h;
+        }
+    };
+    struct Entry { DwPlan p; int tiles; };
+    thread_local std::unordered_map<Key, Entry, Hash> memo;
+    const Key key{op, H, W, C, k, s, pro != 0, epi != 0, variant != 0, cin};
+    auto it = memo.find(key);
+    if (it == memo.end()) {
+        Entry e;
+        e.p = plan_frame(op, H, W, C, k, s, pro != 0, epi != 0, variant != 0, cin, e.tiles);
+        it = memo.emplace(key, e).first;
+    }
+    DwPlan p = it->second.p;
+    p.N = N;
+    p.grid_x = clamp_grid((int64_t)N * it->second.tiles, chunk_cap(max_blocks_x, p.chunks));
+    return p;
+}
+
+}  // namespace dw
+}  // namespace rt1
+
+namespace {
+
+// the kernels' view of a plan's geometry
+inline DwGeo geo_of(const DwPlan& p) {
+    return DwGeo{p.N, p.H, p.W, p.C, p.Ho, p.Wo, p.k, p.s, p.pad, p.nv, p.cv, p.chunks};
+}
+
 template <int EPI>
-int launch_fwd(const bf16_t* x, const float* w, const float* scale, const float* shift, int act, const DwGeo& g,
+int launch_fwd(const DwPlan& p, const bf16_t* x, const float* w, const float* scale, const float* shift, int act,
                int grid_x, bf16_t* out, float* ps, float* pq, BnBwdEpi e, hipStream_t st) {
-    const TileChoice tc = pick_tile(TK_FWD, g.Ho, g.Wo, g.k, g.s, g.cv, scale != nullptr, EPI == EPI_BNBWD);
-    const size_t lds = tile_lds(TK_FWD, g.k, g.s, g.cv, EPI == EPI_BNBWD, tc.TH, tc.TW);
-    dim3 grid(grid_x, g.chunks);
-    const bool ring = g.H * g.W <= DW_RING_PIX;
+    if (p.err) return p.err;
+    const DwGeo g = geo_of(p);
+    dim3 grid(grid_x, p.chunks);
 #define L(KK, SS, RR)                                                                                               \
-    do {                                                                                                            \
-        if (ring)                                                                                                   \
-            hipLaunchKernelGGL((dw_fwd_kernel<KK, SS, RR, EPI, 0, true>), grid, dim3(BLOCK), lds, st, x, w, scale,  \
-                               shift, act, g, tc.TH, tc.TW, out, ps, pq, e, XExp{nullptr, nullptr, 0});             \
+    if (p.k == KK && p.s == SS && p.R == RR) {                                                                      \
+        if (p.ring)                                                                                                 \
+            hipLaunchKernelGGL((dw_fwd_kernel<KK, SS, RR, EPI, 0, true>), grid, dim3(BLOCK), p.lds, st, x, w,       \
+                               scale, shift, act, g, p.TH, p.TW, out, ps, pq, e, XExp{nullptr, nullptr, 0});        \
         else                                                                                                        \
-            hipLaunchKernelGGL((dw_fwd_kernel<KK, SS, RR, EPI>), grid, dim3(BLOCK), lds, st, x, w, scale, shift,    \
-                               act, g, tc.TH, tc.TW, out, ps, pq, e, XExp{nullptr, nullptr, 0});                    \
-    } while (0)
-    const bool r5 = fwd_r(g.s, g.Wo, 0) == 5;
-    if (g.k == 3 && g.s == 1) { if (r5) L(3, 1, 5); else L(3, 1, DW_R1); }
-    else if (g.k == 3 && g.s == 2) L(3, 2, 2);
-    else if (g.k == 5 && g.s == 1) { if (r5) L(5, 1, 5); else L(5, 1, DW_R1); }
-    else if (g.k == 5 && g.s == 2) L(5, 2, 2);
-    else return (int)hipErrorInvalidValue;
+            hipLaunchKernelGGL((dw_fwd_kernel<KK, SS, RR, EPI>), grid, dim3(BLOCK), p.lds, st, x, w, scale, shift,  \
+                               act, g, p.TH, p.TW, out, ps, pq, e, XExp{nullptr, nullptr, 0});                      \
+        return (int)hipGetLastError();                                                                              \
+    }
+    L(3, 1, 5) L(3, 1, DW_R1) L(3, 2, 2) L(5, 1, 5) L(5, 1, DW_R1) L(5, 2, 2)
 #undef L
-    return (int)hipGetLastError();
+    return (int)hipErrorInvalidValue;
 }
 
 }  // namespace
 
 extern "C" {
 
-// Grid helpers: the caller sizes the per-workgroup partial buffers from these, so they must pick the
-// same tile as the launch.  `pro` / `epi` select the cost model of the variant that will run.
+// Grid helpers: the caller sizes the per-workgroup partial buffers from these.  `pro` / `epi` select the cost model
+// of the variant that will run.
 int rt1_dw_grid(int N, int H, int W, int C, int k, int s, int max_blocks_x, int pro, int epi) {
-    DwGeo g = make_geo(N, H, W, C, k, s);
-    const TileChoice tc = pick_tile(TK_FWD, g.Ho, g.Wo, k, s, g.cv, pro != 0, epi != 0);
-    return clamp_grid((int64_t)N * cdiv(g.Ho, tc.TH) * cdiv(g.Wo, tc.TW), chunk_cap(max_blocks_x, g.chunks));
+    return dw_plan(OP_FWD, N, H, W, C, k, s, pro, epi, 0, 0, max_blocks_x).grid_x;
 }
 
 int rt1_dw_wgrad_grid(int N, int H, int W, int C, int k, int s, int max_blocks_x, int pro) {
-    DwGeo g = make_geo(N, H, W, C, k, s);
-    const TileChoice tc = pick_tile(TK_BWD_W, g.Ho, g.Wo, k, s, g.cv, pro != 0, false);
-    return clamp_grid((int64_t)N * cdiv(g.Ho, tc.TH) * cdiv(g.Wo, tc.TW), chunk_cap(max_blocks_x, g.chunks));
+    return dw_plan(OP_BWD_WEIGHT, N, H, W, C, k, s, pro, 0, 0, 0, max_blocks_x).grid_x;
+}
+
+int rt1_dw_bwd_grid(int N, int H, int W, int C, int k, int s, int max_blocks_x, int epi) {
+    return dw_plan(OP_BWD_DATA, N, H, W, C, k, s, 0, epi, 0, 0, max_blocks_x).grid_x;
+}
+
+int rt1_dw_bwd_fused_grid(int N, int H, int W, int C, int k, int max_blocks_x, int pro, int epi, int variant,
+                          int cin) {
+    return dw_plan(OP_BWD_FUSED_S1, N, H, W, C, k, 1, pro, epi, variant, cin, max_blocks_x).grid_x;
+}
+
+int rt1_dw_bwd_fused_s2_grid(int N, int H, int W, int C, int k, int max_blocks_x, int epi, int cin) {
+    return dw_plan(OP_BWD_FUSED_S2, N, H, W, C, k, 2, epi, epi, 1, cin, max_blocks_x).grid_x;
+}
+
+int rt1_dw_grid_x(int N, int H, int W, int C, int k, int s, int cin, int max_blocks_x) {
+    return dw_plan(OP_FWD_X, N, H, W, C, k, s, 1, 0, 0, cin, max_blocks_x).grid_x;
+}
+
+int rt1_dw_bwd_uses_uni(int variant, int pro, int epi) { return use_uni(variant, pro != 0, epi != 0) ? 1 : 0; }
+
+int rt1_dw_x_supported(int cin, int C, int k, int s) { return dw_plan(OP_FWD_X, 1, 8, 8, C, k, s, 1, 0, 0, cin, 1).err == 0; }
+
+// Tile picked for a layer (host-side introspection for tools / tests): which = 0 forward, 1 unified backward
+// (stride 1 or 2); cin > 0 selects x-mode.  out = {TH, TW, LDS bytes, strips per band (0 = all)}.
+int rt1_dw_tile_info(int which, int H, int W, int C, int k, int s, int cin, int* out) {
+    const DwPlan p = which == 0 ? dw_plan(cin > 0 ? OP_FWD_X : OP_FWD, 1, H, W, C, k, s, 1, 0, 0, cin, 1)
+                                : dw_plan(s == 2 ? OP_BWD_FUSED_S2 : OP_BWD_FUSED_S1, 1, H, W, C, k, s, 1, 1, 1, cin, 1);
+    if (cin > 0 && !p.xk) return (int)hipErrorInvalidValue;
+    out[0] = p.TH;
+    out[1] = p.TW;
+    out[2] = p.lds;
+    out[3] = p.sb;
+    return 0;
 }
 
 int rt1_dw_fwd(const bf16_t* x, const float* w, const float* scale, const float* shift, int act, int N, int H, int W,
                int C, int k, int s, int grid_x, bf16_t* out, float* psum, float* psq, hipStream_t st) {
-    DwGeo g = make_geo(N, H, W, C, k, s);
+    const DwPlan p = dw_plan(OP_FWD, N, H, W, C, k, s, scale != nullptr, 0, 0, 0, grid_x);
     BnBwdEpi e{nullptr, nullptr, nullptr, nullptr, nullptr, 0};
-    return psum ? launch_fwd<EPI_STATS>(x, w, scale, shift, act, g, grid_x, out, psum, psq, e, st)
-                : launch_fwd<EPI_NONE>(x, w, scale, shift, act, g, grid_x, out, psum, psq, e, st);
-}
-
-// grid over the INPUT space (the backward output)
-int rt1_dw_bwd_grid(int N, int H, int W, int C, int k, int s, int max_blocks_x, int epi) {
-    DwGeo g = make_geo(N, H, W, C, k, s);
-    TileChoice tc;
-    if (s == 1) tc = pick_tile(TK_FWD, H, W, k, 1, g.cv, false, epi != 0);
-    else tc = pick_tile(TK_BWD_S2, H, W, k, 2, g.cv, false, epi != 0);
-    return clamp_grid((int64_t)N * cdiv(H, tc.TH) * cdiv(W, tc.TW), chunk_cap(max_blocks_x, g.chunks));
+    return psum ? launch_fwd<EPI_STATS>(p, x, w, scale, shift, act, grid_x, out, psum, psq, e, st)
+                : launch_fwd<EPI_NONE>(p, x, w, scale, shift, act, grid_x, out, psum, psq, e, st);
 }
 
 // wflip: the kernel with taps reversed (host prepares it) -- used for s == 1
 int rt1_dw_bwd_data(const bf16_t* dy, const float* w, const float* wflip, int N, int H, int W, int C, int k, int s,
                     int grid_x, bf16_t* dx, const bf16_t* y_in, const float* scale, const float* shift,
                     const float* mean, const float* rstd, float* pdz, float* pdzx, hipStream_t st) {
-    DwGeo g = make_geo(N, H, W, C, k, s);
+    const int epi = y_in != nullptr;
+    const DwPlan p = dw_plan(OP_BWD_DATA, N, H, W, C, k, s, 0, epi, 0, 0, grid_x);
     BnBwdEpi e{y_in, scale, shift, mean, rstd, 0};
-    if (s == 1) {
-        // as a forward over dy (H == Ho for s == 1) with flipped taps
-        DwGeo gd = make_geo(N, g.Ho, g.Wo, C, k, 1);
-        return y_in ? launch_fwd<EPI_BNBWD>(dy, wflip, nullptr, nullptr, 0, gd, grid_x, dx, pdz, pdzx, e, st)
-                    : launch_fwd<EPI_NONE>(dy, wflip, nullptr, nullptr, 0, gd, grid_x, dx, pdz, pdzx, e, st);
-    }
-    const bool epi = y_in != nullptr;
-    const TileChoice tc = pick_tile(TK_BWD_S2, H, W, k, 2, g.cv, false, epi);
-    const size_t lds = tile_lds(TK_BWD_S2, k, 2, g.cv, epi, tc.TH, tc.TW);
-    dim3 grid(grid_x, g.chunks);
-#define L(KK, EE)                                                                                                  \
-    hipLaunchKernelGGL((dw_bwd_data_s2_kernel<KK, EE>), grid, dim3(BLOCK), lds, st, dy, w, g, tc.TH, tc.TW, dx, pdz, \
+    if (p.kind == TK_FWD)
+        return epi ? launch_fwd<EPI_BNBWD>(p, dy, wflip, nullptr, nullptr, 0, grid_x, dx, pdz, pdzx, e, st)
+                   : launch_fwd<EPI_NONE>(p, dy, wflip, nullptr, nullptr, 0, grid_x, dx, pdz, pdzx, e, st);
+    if (p.err) return p.err;
+    const DwGeo g = geo_of(p);
+    dim3 grid(grid_x, p.chunks);
+#define L(KK, EE)                                                                                                   \
+    hipLaunchKernelGGL((dw_bwd_data_s2_kernel<KK, EE>), grid, dim3(BLOCK), p.lds, st, dy, w, g, p.TH, p.TW, dx, pdz, \
                        pdzx, e)
     if (k == 3) { if (epi) L(3, EPI_BNBWD); else L(3, EPI_NONE); }
     else if (k == 5) { if (epi) L(5, EPI_BNBWD); else L(5, EPI_NONE); }
@@ -2453,25 +2413,47 @@ int rt1_dw_bwd_data(const bf16_t* dy, const float* w, const float* wflip, int N,
     return (int)hipGetLastError();
 }
 
-// fused stride-1 backward (dw_bwd_fused_kernel): grid over the H x W map
-int rt1_dw_bwd_fused_grid(int N, int H, int W, int C, int k, int max_blocks_x, int pro, int epi, int variant,
-                          int cin) {
-    DwGeo g = make_geo(N, H, W, C, k, 1);
-    const bool uni = use_uni(variant, pro != 0, epi != 0);
-    const int xk = (cin > 0 && uni) ? xk_of(cin, C, k, 1) : 0;
-    const int kind = uni ? uni_kind(k, xk, H, W) : TK_BWD_F;
-    const TileChoice tc = pick_tile(kind, H, W, k, 1, g.cv, pro != 0, epi != 0, xk);
-    return clamp_grid((int64_t)N * cdiv(H, tc.TH) * cdiv(W, tc.TW), chunk_cap(max_blocks_x, g.chunks));
+// ---- x-mode forward: out = dwconv(silu(bn1(x @ we^T))) with the BN2-stat epilogue; y1 is never stored
+int rt1_dw_fwd_x(const bf16_t* x, int cin, const bf16_t* we, const float* w, const float* scale1, const float* shift1,
+                 int N, int H, int W, int C, int k, int s, int grid_x, bf16_t* out, float* psum, float* psq,
+                 hipStream_t st) {
+    const DwPlan p = dw_plan(OP_FWD_X, N, H, W, C, k, s, 1, 0, 0, cin, grid_x);
+    if (p.err || !scale1 || !shift1 || !psum || !psq) return (int)hipErrorInvalidValue;
+    const DwGeo g = geo_of(p);
+    const BnBwdEpi e{nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+    const XExp xe{x, we, cin};
+    dim3 grid(grid_x, p.chunks);
+#define L(KK, SS, RR, XX)                                                                                           \
+    if (p.k == KK && p.s == SS && p.xk == XX && p.R == RR) {                                                        \
+        hipLaunchKernelGGL((dw_fwd_kernel<KK, SS, RR, EPI_STATS, XX>), grid, dim3(BLOCK), p.lds, st, nullptr, w,    \
+                           scale1, shift1, (int)ACT_SILU, g, p.TH, p.TW, out, psum, psq, e, xe);                    \
+        return (int)hipGetLastError();                                                                              \
+    }
+#define X1(KK, XX) L(KK, 1, DW_R1, XX)
+#define X2(KK, XX) L(KK, 2, 2, XX)
+    DW_XMODE_S1(X1) DW_XMODE_S2(X2)
+#undef X2
+#undef X1
+#undef L
+    return (int)hipErrorInvalidValue;
 }
 
-int rt1_dw_bwd_uses_uni(int variant, int pro, int epi) { return use_uni(variant, pro != 0, epi != 0) ? 1 : 0; }
-
-// unified stride-2 backward: grid over the INPUT map (the dx / centre space)
-int rt1_dw_bwd_fused_s2_grid(int N, int H, int W, int C, int k, int max_blocks_x, int epi, int cin) {
-    DwGeo g = make_geo(N, H, W, C, k, 2);
-    const int xk = cin > 0 ? xk_of(cin, C, k, 2) : 0;
-    const TileChoice tc = pick_tile(uni2_kind(k), H, W, k, 2, g.cv, epi != 0, epi != 0, xk);
-    return clamp_grid((int64_t)N * cdiv(H, tc.TH) * cdiv(W, tc.TW), chunk_cap(max_blocks_x, g.chunks));
+int rt1_dw_bwd_weight(const bf16_t* dy, const bf16_t* x, const float* scale, const float* shift, int act, int N, int H,
+                      int W, int C, int k, int s, int grid_x, float* dwp, hipStream_t st) {
+    const DwPlan p = dw_plan(OP_BWD_WEIGHT, N, H, W, C, k, s, scale != nullptr, 0, 0, 0, grid_x);
+    if (p.err) return p.err;
+    const DwGeo g = geo_of(p);
+    dim3 grid(grid_x, p.chunks);
+#define L(KK, SS, RR)                                                                                               \
+    hipLaunchKernelGGL((dw_bwd_weight_kernel<KK, SS, RR>), grid, dim3(BLOCK), p.lds, st, dy, x, scale, shift, act, \
+                       g, p.TH, p.TW, dwp)
+    if (k == 3 && s == 1) L(3, 1, DW_R1);
+    else if (k == 3 && s == 2) L(3, 2, 2);
+    else if (k == 5 && s == 1) L(5, 1, DW_R1);
+    else if (k == 5 && s == 2) L(5, 2, 2);
+    else return (int)hipErrorInvalidValue;
+#undef L
+    return (int)hipGetLastError();
 }
 
 // dA, y2 [N, Ho, Wo, C]; x1 [N, H, W, C]; w unflipped [C, k*k].  BN1 epilogue (and BN1+SiLU operand) when mean1 is set.
@@ -2481,44 +2463,33 @@ int rt1_dw_bwd_fused_s2(const bf16_t* dA, const bf16_t* y2, const float* gate, c
                         const float* shift1, const float* mean1, const float* rstd1, int N, int H, int W, int C, int k,
                         int grid_x, bf16_t* dx, float* pdz, float* pdzx, float* dwp, hipStream_t st, int zout,
                         const bf16_t* xin, const bf16_t* we, int cin) {
-    DwGeo g = make_geo(N, H, W, C, k, 2);
-    DyBnBwd d{dA, y2, gate, rb, scale2, shift2, mean2, rstd2, gamma2, mdz2, mdzx2};
     const bool epi = mean1 != nullptr;
     if (epi != (scale1 != nullptr) || (zout && !epi)) return (int)hipErrorInvalidValue;
-    // x-mode: y1 recomputed from (xin, we); needs the BN1 epilogue
-    const int xk = xin ? xk_of(cin, C, k, 2) : 0;
-    if (xin && (!xk || !epi || !we)) return (int)hipErrorInvalidValue;
+    // x-mode: y1 recomputed from (xin, we); the plan accepts it with the BN1 epilogue only
+    if (xin && (cin <= 0 || !we)) return (int)hipErrorInvalidValue;
+    const DwPlan p = dw_plan(OP_BWD_FUSED_S2, N, H, W, C, k, 2, epi, epi, 1, xin ? cin : 0, grid_x);
+    if (p.err) return p.err;
+    const DwGeo g = geo_of(p);
+    DyBnBwd d{dA, y2, gate, rb, scale2, shift2, mean2, rstd2, gamma2, mdz2, mdzx2};
     BnBwdEpi e{epi ? x1 : nullptr, scale1, shift1, mean1, rstd1, zout ? 1 : 0};
-    const int kind = uni2_kind(k);
-    const TileChoice tc = pick_tile(kind, H, W, k, 2, g.cv, epi, epi, xk);
-    if ((tc.TH & 1) || (tc.TW % (2 * uni2_r(k)))) return (int)hipErrorInvalidValue;
-    const size_t lds = tile_lds(kind, k, 2, g.cv, epi, tc.TH, tc.TW, xk);
-    const size_t per_tap = (size_t)(BLOCK / (g.cv * 8 / kind_cpt(kind))) * g.cv * 8 * 4;
-    const int red_taps = (int)std::min<size_t>((size_t)k * k, lds / per_tap);
-    dim3 grid(grid_x, g.chunks);
+    dim3 grid(grid_x, p.chunks);
     const XExp xe{xin, we, cin};
-    const bool ring = g.Ho * g.Wo <= DW_RING_PIX;   // the staged dy map
 #define LV1(KK, RR, EE, CC, XX, RGV)                                                                                \
-    hipLaunchKernelGGL((dw_bwd_uni_s2_kernel<KK, RR, EE, CC, XX, RGV>), grid, dim3(BLOCK), lds, st, d, x1, w, g,     \
-                       tc.TH, tc.TW, e, dx, pdz, pdzx, dwp, red_taps, xe)
+    hipLaunchKernelGGL((dw_bwd_uni_s2_kernel<KK, RR, EE, CC, XX, RGV>), grid, dim3(BLOCK), p.lds, st, d, x1, w, g,   \
+                       p.TH, p.TW, e, dx, pdz, pdzx, dwp, p.red_taps, xe)
 #define LV(KK, RR, EE, CC, XX)                                                                                      \
-    do {                                                                                                            \
-        if (ring) LV1(KK, RR, EE, CC, XX, true); else LV1(KK, RR, EE, CC, XX, false);                               \
-    } while (0)
-    if (xk) {
-        if (k == 3 && xk == 0x19) LV(3, DWV_R3, EPI_BNBWD, DWV_CPT3, 0x19);
-        else if (k == 3 && xk == 0x13) LV(3, DWV_R3, EPI_BNBWD, DWV_CPT3, 0x13);
-        else if (k == 3 && xk == 0x11) LV(3, DWV_R3, EPI_BNBWD, DWV_CPT3, 0x11);
-        else if (k == 3 && xk == 0x26) LV(3, DWV_R3, EPI_BNBWD, DWV_CPT3, 0x26);
-        else if (k == 5 && xk == 0x14) LV(5, DWV_R5, EPI_BNBWD, DWV_CPT5, 0x14);
-        else return (int)hipErrorInvalidValue;
+    if (p.k == KK && p.R == RR && epi == (EE == EPI_BNBWD) && p.cpt == CC && p.xk == XX) {                          \
+        if (p.ring) LV1(KK, RR, EE, CC, XX, true); else LV1(KK, RR, EE, CC, XX, false);                             \
+        return (int)hipGetLastError();                                                                              \
     }
-    else if (k == 3) { if (epi) LV(3, DWV_R3, EPI_BNBWD, DWV_CPT3, 0); else LV(3, DWV_R3, EPI_NONE, DWV_CPT3, 0); }
-    else if (k == 5) { if (epi) LV(5, DWV_R5, EPI_BNBWD, DWV_CPT5, 0); else LV(5, DWV_R5, EPI_NONE, DWV_CPT5, 0); }
-    else return (int)hipErrorInvalidValue;
+#define XV(KK, XX) LV(KK, (KK == 3 ? DWV_R3 : DWV_R5), EPI_BNBWD, (KK == 3 ? DWV_CPT3 : DWV_CPT5), XX)
+    DW_XMODE_S2(XV)
+    LV(3, DWV_R3, EPI_BNBWD, DWV_CPT3, 0) LV(3, DWV_R3, EPI_NONE, DWV_CPT3, 0)
+    LV(5, DWV_R5, EPI_BNBWD, DWV_CPT5, 0) LV(5, DWV_R5, EPI_NONE, DWV_CPT5, 0)
+#undef XV
 #undef LV
 #undef LV1
-    return (int)hipGetLastError();
+    return (int)hipErrorInvalidValue;
 }
 
 // dA, y2: the block's dA (grad of the project-conv input before the gate) and the dw output (pre-BN2);
@@ -2531,144 +2502,49 @@ int rt1_dw_bwd_fused(const bf16_t* dA, const bf16_t* y2, const float* gate, cons
                      int H, int W, int C, int k, int grid_x, bf16_t* dx, float* pdz, float* pdzx, float* dwp,
                      hipStream_t st, int variant, int zout, const bf16_t* xin, const bf16_t* we, int cin,
                      const bf16_t* res, const float* rmul) {
-    DwGeo g = make_geo(N, H, W, C, k, 1);
-    DyBnBwd d{dA, y2, gate, rb, scale2, shift2, mean2, rstd2, gamma2, mdz2, mdzx2};
-    const bool epi = mean1 != nullptr;
-    BnBwdEpi e{epi ? x1 : nullptr, scale1, shift1, mean1, rstd1, zout ? 1 : 0, res, rmul};
+    const bool pro = scale1 != nullptr, epi = mean1 != nullptr;
+    // x-mode (y1 recomputed from xin, we): the plan accepts it for the unified kernel with the BN1 epilogue only
+    if (xin && (cin <= 0 || !we)) return (int)hipErrorInvalidValue;
+    const DwPlan p = dw_plan(OP_BWD_FUSED_S1, N, H, W, C, k, 1, pro, epi, variant, xin ? cin : 0, grid_x);
+    if (p.err) return p.err;
+    const bool uni = is_uni(p.kind);
     // the residual epilogue lives in the unified kernel's plain (no BN1) store
-    if (res && (epi || !rmul || !use_uni(variant, scale1 != nullptr, epi))) return (int)hipErrorInvalidValue;
+    if (res && (epi || !rmul || !uni)) return (int)hipErrorInvalidValue;
     // dz output (zout) only from the unified kernel's BN1 epilogue
-    if (zout && !(epi && use_uni(variant, scale1 != nullptr, epi))) return (int)hipErrorInvalidValue;
-    // x-mode (y1 recomputed from xin, we): unified kernel with the BN1 epilogue only
-    const int xk = xin ? xk_of(cin, C, k, 1) : 0;
-    if (xin && (!xk || !epi || !we || !use_uni(variant, scale1 != nullptr, epi))) return (int)hipErrorInvalidValue;
-    if (use_uni(variant, scale1 != nullptr, epi)) {   // w: unflipped (the kernel flips while staging it)
+    if (zout && !(epi && uni)) return (int)hipErrorInvalidValue;
+    const DwGeo g = geo_of(p);
+    DyBnBwd d{dA, y2, gate, rb, scale2, shift2, mean2, rstd2, gamma2, mdz2, mdzx2};
+    BnBwdEpi e{epi ? x1 : nullptr, scale1, shift1, mean1, rstd1, zout ? 1 : 0, res, rmul};
+    dim3 grid(grid_x, p.chunks);
+    if (uni) {   // w: unflipped (the kernel flips while staging it)
         if (epi && act1 != ACT_SILU) return (int)hipErrorInvalidValue;   // the centre prologue is BN + SiLU
-        const int kind = uni_kind(k, xk, H, W);
-        const TileChoice tc = pick_tile(kind, H, W, k, 1, g.cv, scale1 != nullptr, epi, xk);
-        const int sb = xk ? tc.sb : 0;
-        const size_t lds = tile_lds(kind, k, 1, g.cv, epi, tc.TH, tc.TW, xk, sb, W);
-        const int cpt = kind_cpt(kind);
-        const size_t per_tap = (size_t)(BLOCK / (g.cv * 8 / cpt)) * g.cv * 8 * 4;
-        const int red_taps = (int)std::min<size_t>((size_t)k * k, lds / per_tap);
-        dim3 grid(grid_x, g.chunks);
         const XExp xe{xin, we, cin};
-        const bool ring = H * W <= DW_RING_PIX;
 #define LU1(KK, RR, EE, CC, XX, RGV)                                                                                \
-    hipLaunchKernelGGL((dw_bwd_uni_kernel<KK, RR, EE, CC, XX, RGV>), grid, dim3(BLOCK), lds, st, d, x1, w, g,        \
-                       tc.TH, tc.TW, e, dx, pdz, pdzx, dwp, red_taps, xe, sb)
+    hipLaunchKernelGGL((dw_bwd_uni_kernel<KK, RR, EE, CC, XX, RGV>), grid, dim3(BLOCK), p.lds, st, d, x1, w, g,      \
+                       p.TH, p.TW, e, dx, pdz, pdzx, dwp, p.red_taps, xe, p.sb)
 #define LU(KK, RR, EE, CC, XX)                                                                                      \
-    do {                                                                                                            \
-        if (ring) LU1(KK, RR, EE, CC, XX, true); else LU1(KK, RR, EE, CC, XX, false);                               \
-    } while (0)
-        if (xk) {
-            if (k == 3 && xk == 0x14) LU(3, DWU_R3, EPI_BNBWD, DWU_CPT3, 0x14);
-            else if (k == 5 && xk == 0x26) LU(5, DWU_R5, EPI_BNBWD, DWU_CPT5, 0x26);
-            else return (int)hipErrorInvalidValue;
-        }
-        else if (k == 3) { if (epi) LU(3, DWU_R3, EPI_BNBWD, DWU_CPT3, 0); else LU(3, DWU_R3, EPI_NONE, DWU_CPT3, 0); }
-        else if (k == 5 && cpt == 2 && uni_r(5, W, 0, 2) == 5) {
-            if (epi) LU(5, 5, EPI_BNBWD, 2, 0); else LU(5, 5, EPI_NONE, 2, 0);
-        }
-        else if (k == 5 && cpt == 2) { if (epi) LU(5, 4, EPI_BNBWD, 2, 0); else LU(5, 4, EPI_NONE, 2, 0); }
-        else if (k == 5 && uni_r(5, W, 0) == 5) {
-            if (epi) LU(5, 5, EPI_BNBWD, DWU_CPT5, 0); else LU(5, 5, EPI_NONE, DWU_CPT5, 0);
-        }
-        else if (k == 5) { if (epi) LU(5, DWU_R5, EPI_BNBWD, DWU_CPT5, 0); else LU(5, DWU_R5, EPI_NONE, DWU_CPT5, 0); }
-        else return (int)hipErrorInvalidValue;
+    if (p.k == KK && p.R == RR && epi == (EE == EPI_BNBWD) && p.cpt == CC && p.xk == XX) {                          \
+        if (p.ring) LU1(KK, RR, EE, CC, XX, true); else LU1(KK, RR, EE, CC, XX, false);                             \
+        return (int)hipGetLastError();                                                                              \
+    }
+#define XU(KK, XX) LU(KK, (KK == 3 ? DWU_R3 : DWU_R5), EPI_BNBWD, (KK == 3 ? DWU_CPT3 : DWU_CPT5), XX)
+        DW_XMODE_S1(XU)
+        LU(3, DWU_R3, EPI_BNBWD, DWU_CPT3, 0) LU(3, DWU_R3, EPI_NONE, DWU_CPT3, 0)
+        LU(5, 5, EPI_BNBWD, 2, 0) LU(5, 5, EPI_NONE, 2, 0)
+        LU(5, 4, EPI_BNBWD, 2, 0) LU(5, 4, EPI_NONE, 2, 0)
+        LU(5, 5, EPI_BNBWD, DWU_CPT5, 0) LU(5, 5, EPI_NONE, DWU_CPT5, 0)
+        LU(5, DWU_R5, EPI_BNBWD, DWU_CPT5, 0) LU(5, DWU_R5, EPI_NONE, DWU_CPT5, 0)
+#undef XU
 #undef LU
 #undef LU1
-        return (int)hipGetLastError();
+        return (int)hipErrorInvalidValue;
     }
     if (y2 == nullptr) return (int)hipErrorInvalidValue;   // copy staging (dA = dy) is a unified-kernel mode
-    const TileChoice tc = pick_tile(TK_BWD_F, H, W, k, 1, g.cv, scale1 != nullptr, epi);
-    const size_t lds = tile_lds(TK_BWD_F, k, 1, g.cv, epi, tc.TH, tc.TW);
-    dim3 grid(grid_x, g.chunks);
-#define L(KK, EE)                                                                                                  \
-    hipLaunchKernelGGL((dw_bwd_fused_kernel<KK, DW_R1, EE>), grid, dim3(BLOCK), lds, st, d, x1, scale1, shift1, \
-                       act1, wflip, g, tc.TH, tc.TW, dx, pdz, pdzx, e, dwp)
+#define L(KK, EE)                                                                                                   \
+    hipLaunchKernelGGL((dw_bwd_fused_kernel<KK, DW_R1, EE>), grid, dim3(BLOCK), p.lds, st, d, x1, scale1, shift1,   \
+                       act1, wflip, g, p.TH, p.TW, dx, pdz, pdzx, e, dwp)
     if (k == 3) { if (epi) L(3, EPI_BNBWD); else L(3, EPI_NONE); }
     else if (k == 5) { if (epi) L(5, EPI_BNBWD); else L(5, EPI_NONE); }
-    else return (int)hipErrorInvalidValue;
-#undef L
-    return (int)hipGetLastError();
-}
-
-// Tile picked for a layer (host-side introspection for tools / tests): which = 0 forward, 1 unified backward
-// (stride 1 or 2); cin > 0 selects x-mode.  out = {TH, TW, LDS bytes, strips per band (0 = all)}.
-int rt1_dw_tile_info(int which, int H, int W, int C, int k, int s, int cin, int* out) {
-    const DwGeo g = make_geo(1, H, W, C, k, s);
-    const int xk = cin > 0 ? xk_of(cin, C, k, s) : 0;
-    if (cin > 0 && !xk) return (int)hipErrorInvalidValue;
-    int kind;
-    TileChoice tc;
-    if (which == 0) {
-        kind = TK_FWD;
-        tc = pick_tile(kind, g.Ho, g.Wo, k, s, g.cv, true, false, xk);
-    } else {
-        kind = s == 2 ? uni2_kind(k) : uni_kind(k, xk, H, W);
-        tc = pick_tile(kind, H, W, k, s, g.cv, true, true, xk);
-    }
-    out[0] = tc.TH;
-    out[1] = tc.TW;
-    out[2] = (int)tile_lds(kind, k, s, g.cv, which != 0, tc.TH, tc.TW, xk, tc.sb, W);
-    out[3] = tc.sb;
-    return 0;
-}
-
-// ---- x-mode forward: out = dwconv(silu(bn1(x @ we^T))) with the BN2-stat epilogue; y1 is never stored
-int rt1_dw_x_supported(int cin, int C, int k, int s) {
-    const int xk = xk_of(cin, C, k, s);
-    if (!xk) return 0;
-    if (s == 1) return (k == 3 && xk == 0x14) || (k == 5 && xk == 0x26);
-    return (k == 3 && (xk == 0x19 || xk == 0x13 || xk == 0x11 || xk == 0x26)) || (k == 5 && xk == 0x14);
-}
-
-int rt1_dw_grid_x(int N, int H, int W, int C, int k, int s, int cin, int max_blocks_x) {
-    DwGeo g = make_geo(N, H, W, C, k, s);
-    const TileChoice tc = pick_tile(TK_FWD, g.Ho, g.Wo, k, s, g.cv, true, false, xk_of(cin, C, k, s));
-    return clamp_grid((int64_t)N * cdiv(g.Ho, tc.TH) * cdiv(g.Wo, tc.TW), chunk_cap(max_blocks_x, g.chunks));
-}
-
-int rt1_dw_fwd_x(const bf16_t* x, int cin, const bf16_t* we, const float* w, const float* scale1, const float* shift1,
-                 int N, int H, int W, int C, int k, int s, int grid_x, bf16_t* out, float* psum, float* psq,
-                 hipStream_t st) {
-    DwGeo g = make_geo(N, H, W, C, k, s);
-    const int xk = xk_of(cin, C, k, s);
-    if (!rt1_dw_x_supported(cin, C, k, s) || !scale1 || !shift1 || !psum || !psq) return (int)hipErrorInvalidValue;
-    const TileChoice tc = pick_tile(TK_FWD, g.Ho, g.Wo, k, s, g.cv, true, false, xk);
-    const size_t lds = tile_lds(TK_FWD, k, s, g.cv, false, tc.TH, tc.TW, xk);
-    const BnBwdEpi e{nullptr, nullptr, nullptr, nullptr, nullptr, 0};
-    const XExp xe{x, we, cin};
-    dim3 grid(grid_x, g.chunks);
-#define L(KK, SS, RR, XX)                                                                                           \
-    hipLaunchKernelGGL((dw_fwd_kernel<KK, SS, RR, EPI_STATS, XX>), grid, dim3(BLOCK), lds, st, nullptr, w, scale1, \
-                       shift1, (int)ACT_SILU, g, tc.TH, tc.TW, out, psum, psq, e, xe)
-    if (k == 3 && s == 2 && xk == 0x19) L(3, 2, 2, 0x19);
-    else if (k == 3 && s == 2 && xk == 0x13) L(3, 2, 2, 0x13);
-    else if (k == 3 && s == 2 && xk == 0x11) L(3, 2, 2, 0x11);
-    else if (k == 3 && s == 2 && xk == 0x26) L(3, 2, 2, 0x26);
-    else if (k == 3 && s == 1 && xk == 0x14) L(3, 1, DW_R1, 0x14);
-    else if (k == 5 && s == 2 && xk == 0x14) L(5, 2, 2, 0x14);
-    else if (k == 5 && s == 1 && xk == 0x26) L(5, 1, DW_R1, 0x26);
-    else return (int)hipErrorInvalidValue;
-#undef L
-    return (int)hipGetLastError();
-}
-
-int rt1_dw_bwd_weight(const bf16_t* dy, const bf16_t* x, const float* scale, const float* shift, int act, int N, int H,
-                      int W, int C, int k, int s, int grid_x, float* dwp, hipStream_t st) {
-    DwGeo g = make_geo(N, H, W, C, k, s);
-    const TileChoice tc = pick_tile(TK_BWD_W, g.Ho, g.Wo, k, s, g.cv, scale != nullptr, false);
-    const size_t lds = tile_lds(TK_BWD_W, k, s, g.cv, false, tc.TH, tc.TW);
-    dim3 grid(grid_x, g.chunks);
-#define L(KK, SS, RR)                                                                                               \
-    hipLaunchKernelGGL((dw_bwd_weight_kernel<KK, SS, RR>), grid, dim3(BLOCK), lds, st, dy, x, scale, shift, act, g, \
-                       tc.TH, tc.TW, dwp)
-    if (k == 3 && s == 1) L(3, 1, DW_R1);
-    else if (k == 3 && s == 2) L(3, 2, 2);
-    else if (k == 5 && s == 1) L(5, 1, DW_R1);
-    else if (k == 5 && s == 2) L(5, 2, 2);
     else return (int)hipErrorInvalidValue;
 #undef L
     return (int)hipGetLastError();

@@ -5,24 +5,24 @@ tap t = kh*k + kw, pad (k-1)/2.  Every reference is a sum over the k*k taps of s
 tensor and returns (ref, S) with S the same tap sum over absolute values, S = sum_t |w_t| * S_operand_t (glue_oracle's
 convention: the magnitude that the fp32 roundings are relative to).
 
-What the kernels compute, read from dwconv.hip (line numbers as of the commit that added this file):
-  * Zero padding applies to the operand AFTER its prologue: stage_tile_t / stage_dy_v2 write zeros for the ring and
-    for out-of-image pixels (zero_ring, l. 135-151; `if (!ok[k]) v = 0`, l. 988), the prologue runs only on loaded
-    pixels (l. 209).
-  * A staged operand is bf16 (pack2 before `tile[p * cv + vv] = v`, l. 229-232 and l. 986-989), so the operand
+What the kernels compute, read from dwconv.hip and cited by function:
+  * Zero padding applies to the operand AFTER its prologue: stage_tile_t and stage_dy / stage_dy_half write zeros for
+    the ring and for out-of-image pixels (zero_ring; `if (!ok[k]) v = 0`), the prologue runs only on loaded pixels
+    (stage_tile_t: `if (PRO != PRO_COPY && (valid >> k & 1u))`).
+  * A staged operand is bf16 (pack2 before `tile[p * cv + vv] = v` in stage_tile_t and stage_dy), so the operand
     functions below round the fp64 operand to bf16 before the tap sum.  One exception: the unified backward kernels
-    build a = silu(bn1(x1)) for the WEIGHT product in fp32 registers and never round it (centre_silu, l. 1468:
-    `a[r][j] = ok[r] ? z * t : 0`, used at l. 1692 and l. 1912: `wacc[..] = in[j] * a[r][j] + wacc[..]`), so
-    operand_bn_silu takes round=False for their weight gradient; the two-pass kernel (l. 1272) and dw_bwd_weight
-    (l. 777) stage a through stage_tile as bf16.
-  * Partial sums.  The forward's EPI_STATS sums the STORED bf16 outputs (dw_fwd_kernel, l. 604-615: `unpack4x2(u, v)`
-    of the packed word that was stored).  The EPI_BNBWD epilogue of dw_bwd_data and of the two-pass fused kernel rounds
-    first (epilogue<EPI>, l. 439: `o[j] = bf2f(f2bf(o[j]))`, "statistics describe the stored bf16 tensor") and sums
-    dz = bf16(dx) * silu'(z), dz * xhat with xhat = y * rstd - mean * rstd (l. 456-458).  The unified kernels do the
-    same (dw_bwd_uni_kernel l. 1743-1750, uni_s2_class l. 1944-1951: `CV::unpack(o, of)`; `if (!zout) dz = dz * gp`).
-    With zout they store bf16(dx_fp32 * silu'(z)) -- the fp32 accumulator times silu', one rounding (l. 1725-1728 and
-    l. 1935-1938: `acc[r][j] = acc[r][j] * gp[r][j]` before the pack) -- and sum that stored dz.
-  * res / rmul: `acc = rv * fm + acc` in fp32 before the one rounding of the store (l. 1731-1737).
+    build a = silu(bn1(x1)) for the WEIGHT product in fp32 registers and never round it (centre_silu:
+    `a[r][j] = ok[r] ? z * t : 0`, used in the tap loops of dw_bwd_uni_kernel and uni_s2_class:
+    `wacc[..] = in[j] * a[r][j] + wacc[..]`), so operand_bn_silu takes round=False for their weight gradient; the
+    two-pass kernel (dw_bwd_fused_kernel) and dw_bwd_weight_kernel stage a through stage_tile as bf16.
+  * Partial sums.  The forward's EPI_STATS sums the STORED bf16 outputs (dw_fwd_kernel: `unpack4x2(u, v)` of the
+    packed word that was stored).  The EPI_BNBWD epilogue of dw_bwd_data and of the two-pass fused kernel rounds
+    first (epilogue<EPI>: `o[j] = bf2f(f2bf(o[j]))`, "statistics describe the stored bf16 tensor") and sums
+    dz = bf16(dx) * silu'(z), dz * xhat with xhat = y * rstd - mean * rstd.  The unified kernels do the same (the
+    epilogues of dw_bwd_uni_kernel and uni_s2_class: `CV::unpack(o, of)`; `if (!zout) dz = dz * gp`).  With zout they
+    store bf16(dx_fp32 * silu'(z)) -- the fp32 accumulator times silu', one rounding
+    (`acc[r][j] = acc[r][j] * gp[r][j]` before the pack) -- and sum that stored dz.
+  * res / rmul: `acc = rv * fm + acc` in fp32 before the one rounding of the store (dw_bwd_uni_kernel's epilogue).
   * silu'(z) = s (1 + z (1 - s)) has the addends 1 and z (1 - s), which cancel at z = -1.278: S of a dz output carries
     s (1 + |z| (1 - s)), not |silu'(z)|  (silu_grad_abs).
 

@@ -1,5 +1,6 @@
 #!/bin/bash
-# Build the kernels' host code with ASan + UBSan (host side only) and run the shape sweep on the CPU.
+# Build the kernels' host code with ASan + UBSan (host side only) and run the shape sweep on the CPU
+# (arguments go to the program: --dw-plans prints the depthwise launch plans instead).
 set -euo pipefail
 ROOT="$(cd "$(dirname "$0")/../.." && pwd)"
 OUT="$ROOT/build/asan"
@@ -11,7 +12,11 @@ pids=()
 for s in $SRCS; do
   src="$ROOT/pytorch_rt1_for_distributed_training_amd/csrc/kernels/$s.hip"
   obj="$OUT/$s.o"
-  if [ ! -f "$obj" ] || [ "$src" -nt "$obj" ] || [ "$ROOT/pytorch_rt1_for_distributed_training_amd/csrc/kernels/common.h" -nt "$obj" ]; then
+  stale=0
+  for dep in "$src" "$ROOT"/pytorch_rt1_for_distributed_training_amd/csrc/kernels/common.h "$ROOT"/pytorch_rt1_for_distributed_training_amd/csrc/kernels/dw/*.h; do
+    if [ ! -f "$obj" ] || [ "$dep" -nt "$obj" ]; then stale=1; fi
+  done
+  if [ "$stale" = 1 ]; then
     $HIPCC --offload-arch=gfx950 -std=c++17 -O1 -g $SAN -c "$src" -o "$obj" &
     pids+=($!)
   fi
@@ -19,4 +24,4 @@ done
 for p in "${pids[@]}"; do wait "$p"; done
 $HIPCC -std=c++17 -O1 -g $SAN -c "$ROOT/tools/host_asan/host_checks.cpp" -o "$OUT/host_checks.o"
 $HIPCC --offload-arch=gfx950 -fsanitize=address,undefined -fno-gpu-sanitize -o "$OUT/host_checks" "$OUT"/*.o
-ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 "$OUT/host_checks"
+ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 "$OUT/host_checks" "$@"

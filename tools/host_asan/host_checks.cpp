@@ -6,6 +6,8 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
+#include <initializer_list>
 
 #include "../../pytorch_rt1_for_distributed_training_amd/csrc/rt1_kernels.h"
 
@@ -18,7 +20,99 @@ static int failures = 0;
         }                                                                           \
     } while (0)
 
-int main() {
+// --dw-plans: every host-side launch decision of the depthwise kernels, one line per case (n, h, w, c, k, s), through
+// the extern "C" interface only (tests/test_dw_plan.py compares the output with tests/fixtures/dw_plans.txt):
+//   n h w c k s : f<flag> uses_uni, then per max_blocks_x ("/ mb:") dw_grid wgrad_grid bwd_grid | fused grids
+//   x<cin>=grid_x/fused grid ... ; T<cin> tile_info(which = 0) , tile_info(which = 1), each TH TW lds sb or E<code>
+static void dw_plan_case(int n, int h, int w, int c, int k, int s, std::initializer_list<int> mbs) {
+    std::printf("%d %d %d %d %d %d :", n, h, w, c, k, s);
+    for (int flag = 0; flag < 2; ++flag) {
+        std::printf(" f%d %d%d%d", flag, rt1_dw_bwd_uses_uni(1, flag, flag), rt1_dw_bwd_uses_uni(0, flag, flag),
+                    rt1_dw_bwd_uses_uni(1, flag, 1 - flag));
+        for (int mb : mbs) {
+            std::printf(" / %d: %d %d %d |", mb, rt1_dw_grid(n, h, w, c, k, s, mb, flag, 1 - flag),
+                        rt1_dw_wgrad_grid(n, h, w, c, k, s, mb, flag), rt1_dw_bwd_grid(n, h, w, c, k, s, mb, flag));
+            if (s == 2) std::printf(" %d", rt1_dw_bwd_fused_s2_grid(n, h, w, c, k, mb, flag, 0));
+            else std::printf(" %d %d %d %d", rt1_dw_bwd_fused_grid(n, h, w, c, k, mb, flag, flag, 1, 0),
+                             rt1_dw_bwd_fused_grid(n, h, w, c, k, mb, flag, flag, 0, 0),
+                             rt1_dw_bwd_fused_grid(n, h, w, c, k, mb, flag, 1 - flag, 1, 0),
+                             rt1_dw_bwd_fused_grid(n, h, w, c, k, mb, flag, flag, -1, 0));
+            for (int cin : {24, 32, 48}) {
+                if (!rt1_dw_x_supported(cin, c, k, s)) continue;
+                std::printf(" x%d=%d/%d", cin, rt1_dw_grid_x(n, h, w, c, k, s, cin, mb),
+                            s == 2 ? rt1_dw_bwd_fused_s2_grid(n, h, w, c, k, mb, 1, cin)
+                                   : rt1_dw_bwd_fused_grid(n, h, w, c, k, mb, 1, 1, 1, cin));
+            }
+        }
+    }
+    for (int cin : {0, 24, 32, 48}) {
+        if (cin && !rt1_dw_x_supported(cin, c, k, s)) continue;
+        std::printf(" ; T%d", cin);
+        for (int which = 0; which < 2; ++which) {
+            int o[4] = {-1, -1, -1, -1};
+            const int rc = rt1_dw_tile_info(which, h, w, c, k, s, cin, o);
+            if (rc) std::printf(" E%d", rc);
+            else std::printf(" %d %d %d %d", o[0], o[1], o[2], o[3]);
+            if (!which) std::printf(" ,");
+        }
+    }
+    std::printf("\n");
+}
+
+static int dw_plans() {
+    const int res[] = {150, 128, 75, 64, 38, 32, 19, 16, 10, 8, 5, 1};
+    const int chans[] = {40, 24, 144, 192, 288, 336, 576, 672, 816, 1152, 1392, 2304, 8, 16};
+    // the sweep of main(); frames = 768 only (with the frames = 1 rows the fixture passes 256 KB)
+    for (int h : res)
+        for (int c : chans)
+            for (int k = 3; k <= 5; k += 2)
+                for (int s = 1; s <= 2; ++s) {
+                    const int w = h + 7 * (h % 3);
+                    dw_plan_case(768, h, w, c, k, s, {4096, 64});
+                }
+    // PLAIN, FUSED_S1 and FUSED_S2 of tests/test_dw_oracle_gpu.py: {N, H, W, C, stride, max_blocks, kernel sizes}
+    const int shapes[][7] = {
+        {2, 21, 22, 40, 1, 64, 35},  {1, 45, 46, 24, 1, 64, 35},  {1, 46, 45, 24, 1, 64, 35},  {3, 13, 25, 48, 1, 64, 35},
+        {4, 10, 10, 136, 1, 64, 35}, {3, 19, 19, 152, 1, 64, 35}, {3, 19, 19, 152, 2, 64, 35}, {2, 19, 21, 288, 1, 64, 35},
+        {6, 19, 19, 816, 2, 4, 35},  {8, 10, 10, 1392, 1, 8, 5},  {5, 10, 10, 2304, 1, 5, 3},  {2, 17, 33, 144, 2, 64, 35},
+        {2, 20, 30, 144, 2, 64, 35}, {1, 91, 92, 16, 2, 64, 35},
+        {5, 10, 10, 2304, 1, 5, 3},  {2, 19, 22, 40, 1, 64, 5},   {1, 45, 46, 24, 1, 64, 5},   {2, 20, 20, 48, 1, 64, 5},
+        {3, 19, 19, 152, 1, 64, 5},  {4, 19, 19, 816, 1, 16, 5},  {4, 10, 10, 136, 1, 64, 5},  {3, 15, 25, 96, 1, 64, 5},
+        {2, 13, 15, 40, 1, 64, 5},   {8, 10, 10, 1392, 1, 8, 5},
+        {2, 17, 23, 40, 2, 64, 35},  {2, 20, 30, 144, 2, 64, 35}, {3, 19, 19, 152, 2, 64, 35}, {2, 38, 38, 288, 2, 2048, 35},
+        {1, 91, 92, 16, 2, 64, 35}};
+    for (const auto& q : shapes)
+        for (int k = 3; k <= 5; k += 2) {
+            if (q[6] != 35 && q[6] != k) continue;
+            dw_plan_case(q[0], q[1], q[2], q[3], k, q[4], {q[5]});
+        }
+    // the 26 depthwise layers of the B3 backbone at 300 x 300 input: {map, channels, k, stride, block input channels}
+    const int layers[][5] = {{150, 40, 3, 1, 0},    {150, 24, 3, 1, 0},    {150, 144, 3, 2, 24},  {75, 192, 3, 1, 32},
+                             {75, 192, 3, 1, 32},   {75, 192, 5, 2, 32},   {38, 288, 5, 1, 48},   {38, 288, 5, 1, 48},
+                             {38, 288, 3, 2, 48},   {19, 576, 3, 1, 96},   {19, 576, 3, 1, 96},   {19, 576, 3, 1, 96},
+                             {19, 576, 3, 1, 96},   {19, 576, 5, 1, 96},   {19, 816, 5, 1, 136},  {19, 816, 5, 1, 136},
+                             {19, 816, 5, 1, 136},  {19, 816, 5, 1, 136},  {19, 816, 5, 2, 136},  {10, 1392, 5, 1, 232},
+                             {10, 1392, 5, 1, 232}, {10, 1392, 5, 1, 232}, {10, 1392, 5, 1, 232}, {10, 1392, 5, 1, 232},
+                             {10, 1392, 3, 1, 232}, {10, 2304, 3, 1, 384}};
+    for (const auto& l : layers)
+        for (int n : {768, 6}) {
+            dw_plan_case(n, l[0], l[0], l[1], l[2], l[3], {4096, 2048});
+            const int cin = l[4];
+            if (cin && rt1_dw_x_supported(cin, l[1], l[2], l[3])) {
+                int o[4] = {-1, -1, -1, -1};
+                const int rc = rt1_dw_tile_info(1, l[0], l[0], l[1], l[2], l[3], cin, o);
+                std::printf("L %d %d %d %d %d %d : %d %d | %d %d %d %d %d\n", n, l[0], l[1], l[2], l[3], cin,
+                            rt1_dw_grid_x(n, l[0], l[0], l[1], l[2], l[3], cin, 4096),
+                            l[3] == 2 ? rt1_dw_bwd_fused_s2_grid(n, l[0], l[0], l[1], l[2], 4096, 1, cin)
+                                      : rt1_dw_bwd_fused_grid(n, l[0], l[0], l[1], l[2], 4096, 1, 1, 1, cin),
+                            rc, o[0], o[1], o[2], o[3]);
+            }
+        }
+    return 0;
+}
+
+int main(int argc, char** argv) {
+    if (argc > 1 && std::strcmp(argv[1], "--dw-plans") == 0) return dw_plans();
     // depthwise grids: every (resolution, channel, kernel, stride) family of B3 at three input sizes
     const int res[] = {150, 128, 75, 64, 38, 32, 19, 16, 10, 8, 5, 1};
     const int chans[] = {40, 24, 144, 192, 288, 336, 576, 672, 816, 1152, 1392, 2304, 8, 16};
