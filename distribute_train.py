@@ -61,6 +61,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--skip_nonfinite_steps", action="store_true",
                    help="a step whose gradient norm is not finite changes nothing: no Adam update, BN running "
                         "statistics rolled back")
+    p.add_argument("--accumulate_grad_batches", type=int, default=1,
+                   help="optimizer step every N batches on the mean of their gradients (Lightning's name; N x "
+                        "--batch_size on one GPU computes the mean gradient of N data-parallel ranks)")
     p.add_argument("--bucket_cap_mb", type=float, default=32.0)
     p.add_argument("--no_broadcast_buffers", action="store_true")
     p.add_argument("--comm", choices=["torch", "native"], default="torch",
@@ -207,10 +210,12 @@ def train(args):
                          bucket_cap_mb=args.bucket_cap_mb, broadcast_buffers=not args.no_broadcast_buffers,
                          comm=args.comm, graph=use_graph,
                          max_grad_norm=args.gradient_clip_val if args.gradient_clip_val > 0 else None,
-                         skip_nonfinite=args.skip_nonfinite_steps)
+                         skip_nonfinite=args.skip_nonfinite_steps,
+                         accumulate_grad_batches=args.accumulate_grad_batches)
     if ctx.is_main:
         print(f"[train] gradient_clip_val {args.gradient_clip_val if args.gradient_clip_val > 0 else 'off'}, "
-              f"skip_nonfinite_steps {'on' if args.skip_nonfinite_steps else 'off'}", flush=True)
+              f"skip_nonfinite_steps {'on' if args.skip_nonfinite_steps else 'off'}, "
+              f"accumulate_grad_batches {args.accumulate_grad_batches}", flush=True)
     ckpt = ModelCheckpoint(os.path.join(args.ckpt_dir, args.exp_name), every_n_epochs=args.ckpt_every_n_epochs)
     loggers = []
     if ctx.is_main:

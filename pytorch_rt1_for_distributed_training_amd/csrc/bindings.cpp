@@ -243,6 +243,60 @@ void multi_reduce_copy_(std::vector<at::Tensor> dst, std::vector<at::Tensor> src
     }
 }
 
+// Gradient accumulation over several backwards (FlatParameters.gather_grads(accumulate=True)): the accumulating forms
+// of the two gathers above.  dst[i] += src[i] for contiguous fp32 GPU tensors of equal numel, 128 per launch
+void multi_add_(std::vector<at::Tensor> dst, std::vector<at::Tensor> src) {
+    TORCH_CHECK(dst.size() == src.size(), "multi_add_: list lengths differ");
+    std::vector<const float*> sp;
+    std::vector<float*> dp;
+    std::vector<int64_t> np;
+    for (size_t i = 0; i < dst.size(); ++i) {
+        const auto& d = dst[i];
+        const auto& s = src[i];
+        TORCH_CHECK(d.is_cuda() && s.is_cuda() && d.scalar_type() == at::kFloat && s.scalar_type() == at::kFloat &&
+                    d.is_contiguous() && s.is_contiguous() && d.numel() == s.numel(),
+                    "multi_add_: contiguous fp32 GPU tensors of equal size (entry ", i, ")");
+        if (d.numel() == 0) continue;
+        sp.push_back(s.data_ptr<float>());
+        dp.push_back(d.data_ptr<float>());
+        np.push_back(d.numel());
+    }
+    for (size_t o = 0; o < sp.size(); o += 128) {
+        const int cnt = (int)std::min<size_t>(128, sp.size() - o);
+        check_launch(rt1_multi_add(sp.data() + o, dp.data() + o, np.data() + o, cnt, cur_stream()), "multi_add_");
+    }
+}
+
+// dst[i] = dst[i] + (the split sum multi_reduce_copy_ forms, in the same order): bitwise old + multi_reduce_copy_(...)
+void multi_reduce_add_(std::vector<at::Tensor> dst, std::vector<at::Tensor> src, std::vector<int64_t> splits,
+                       std::vector<int64_t> sstride) {
+    TORCH_CHECK(dst.size() == src.size() && dst.size() == splits.size() && dst.size() == sstride.size(),
+                "multi_reduce_add_: list lengths differ");
+    std::vector<const float*> sp;
+    std::vector<float*> dp;
+    std::vector<int64_t> np, ssp;
+    std::vector<int> kp;
+    for (size_t i = 0; i < dst.size(); ++i) {
+        const auto& d = dst[i];
+        const auto& s = src[i];
+        TORCH_CHECK(d.is_cuda() && s.is_cuda() && d.scalar_type() == at::kFloat && s.scalar_type() == at::kFloat &&
+                    d.is_contiguous() && s.is_contiguous() && d.numel() == s.numel() && splits[i] >= 1 &&
+                    (splits[i] == 1 || sstride[i] >= s.numel()),
+                    "multi_reduce_add_: contiguous fp32 GPU tensors of equal size, splits >= 1 (entry ", i, ")");
+        if (d.numel() == 0) continue;
+        sp.push_back(s.data_ptr<float>());
+        dp.push_back(d.data_ptr<float>());
+        np.push_back(d.numel());
+        ssp.push_back(sstride[i]);
+        kp.push_back((int)splits[i]);
+    }
+    for (size_t o = 0; o < sp.size(); o += 128) {
+        const int cnt = (int)std::min<size_t>(128, sp.size() - o);
+        check_launch(rt1_multi_reduce_add(sp.data() + o, dp.data() + o, np.data() + o, ssp.data() + o, kp.data() + o,
+                                          cnt, cur_stream()), "multi_reduce_add_");
+    }
+}
+
 // raw [N, h, w, 3] uint8 frames + boxes [N, 4] int32 (x0, y0, x1, y1) -> [N, 3, H, W] uint8 (Pillow bilinear)
 at::Tensor crop_resize_u8(at::Tensor raw, at::Tensor boxes, int64_t H, int64_t W) {
     TORCH_CHECK(raw.is_cuda() && raw.is_contiguous() && raw.scalar_type() == at::kByte && raw.dim() == 4 &&
@@ -1492,6 +1546,9 @@ PYBIND11_MODULE(_rt1_hip, m) {
     m.def("multi_reduce_copy_", &multi_reduce_copy_, "dst[i] = fixed-order sum of splits[i] partials of src[i]",
           py::arg("dst"), py::arg("src"), py::arg("splits"), py::arg("sstride"));
     m.def("multi_copy_", &multi_copy_, "dst[i].copy_(src[i]) for many same-dtype tensors, 128 per launch");
+    m.def("multi_reduce_add_", &multi_reduce_add_, "dst[i] += fixed-order sum of splits[i] partials of src[i]",
+          py::arg("dst"), py::arg("src"), py::arg("splits"), py::arg("sstride"));
+    m.def("multi_add_", &multi_add_, "dst[i] += src[i] for many fp32 tensors, 128 per launch");
     m.def("colsum", &colsum_py, "deterministic fixed-order sum over dim 0 (fp32/bf16 in, fp32 out)");
     m.def("frame_pool", &frame_pool);
     m.def("block_tail", &block_tail);

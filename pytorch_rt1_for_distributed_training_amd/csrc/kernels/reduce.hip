@@ -122,6 +122,8 @@ struct CopyList {
     int64_t n[MC_MAX];
 };
 
+// ACC (gradient accumulation over several backwards, multi_add_): dst[e] += src[e] instead, one more read stream.
+template <bool ACC>
 __global__ __launch_bounds__(256) void multi_copy_kernel(CopyList L) {
     const int i = blockIdx.y;
     const float* __restrict__ s = L.src[i];
@@ -132,11 +134,20 @@ __global__ __launch_bounds__(256) void multi_copy_kernel(CopyList L) {
     int64_t head = 0;
     if (vec) {
         const int64_t nv = n / 4;
-        for (int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x; v < nv; v += stride)
-            reinterpret_cast<float4*>(d)[v] = reinterpret_cast<const float4*>(s)[v];
+        for (int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x; v < nv; v += stride) {
+            float4 a = reinterpret_cast<const float4*>(s)[v];
+            if constexpr (ACC) {
+                const float4 o = reinterpret_cast<const float4*>(d)[v];
+                a.x += o.x; a.y += o.y; a.z += o.z; a.w += o.w;
+            }
+            reinterpret_cast<float4*>(d)[v] = a;
+        }
         head = nv * 4;
     }
-    for (int64_t e = head + (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += stride) d[e] = s[e];
+    for (int64_t e = head + (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += stride) {
+        if constexpr (ACC) d[e] += s[e];
+        else d[e] = s[e];
+    }
 }
 
 // Gradient gather with the split-K sums folded in: dst[e] = sum_{k < splits} src[k * sstride + e], k in order (a
@@ -156,6 +167,9 @@ struct ReduceList {
 // in order (4 loads in flight), then the G group sums combine in LDS as ((s0 + s1) + s2) + ...  Entries with many
 // splits and few elements (the deep layers' split-K partials: 64-256 splits of a few thousand weights) get G = 16,
 // so their sums are not one long dependent chain per thread.  Fixed order throughout: same inputs, same bits.
+// ACC (multi_reduce_add_): the split sum is formed exactly as above and the destination's old value is added once,
+// last -- bitwise old + multi_reduce_copy_(...), and multi_reduce_copy_ itself on a zeroed destination.
+template <bool ACC>
 __global__ __launch_bounds__(256) void multi_reduce_copy_kernel(ReduceList L) {
     __shared__ float4 red[256];
     const int i = blockIdx.y;
@@ -188,7 +202,13 @@ __global__ __launch_bounds__(256) void multi_reduce_copy_kernel(ReduceList L) {
                 }
             }
             if (G == 1) {
-                if (v < nv) reinterpret_cast<float4*>(d)[v] = a;
+                if (v < nv) {
+                    if constexpr (ACC) {
+                        const float4 o = reinterpret_cast<const float4*>(d)[v];
+                        a.x += o.x; a.y += o.y; a.z += o.z; a.w += o.w;
+                    }
+                    reinterpret_cast<float4*>(d)[v] = a;
+                }
                 continue;
             }
             __syncthreads();                                       // previous round's LDS reads are done
@@ -199,6 +219,10 @@ __global__ __launch_bounds__(256) void multi_reduce_copy_kernel(ReduceList L) {
                     const float4 b = red[h * CW + c];
                     a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
                 }
+                if constexpr (ACC) {
+                    const float4 o = reinterpret_cast<const float4*>(d)[v];
+                    a.x += o.x; a.y += o.y; a.z += o.z; a.w += o.w;
+                }
                 reinterpret_cast<float4*>(d)[v] = a;
             }
         }
@@ -206,6 +230,7 @@ __global__ __launch_bounds__(256) void multi_reduce_copy_kernel(ReduceList L) {
             const int64_t e = nv * 4 + t;
             float x = s[e];
             for (int k = 1; k < S; ++k) x += s[k * ss + e];
+            if constexpr (ACC) x += d[e];
             d[e] = x;
         }
         return;
@@ -213,6 +238,7 @@ __global__ __launch_bounds__(256) void multi_reduce_copy_kernel(ReduceList L) {
     for (int64_t e = (int64_t)blockIdx.x * 256 + t; e < n; e += (int64_t)gridDim.x * 256) {
         float x = s[e];
         for (int k = 1; k < S; ++k) x += s[k * ss + e];
+        if constexpr (ACC) x += d[e];
         d[e] = x;
     }
 }
@@ -252,8 +278,9 @@ int rt1_colsum(const void* in, int in_is_bf16, int64_t R, int C, int B, float* o
     return launch_pass<float>(tmp, chunks, C, B, (int64_t)chunks * C, chunks, 1, out, C, st);
 }
 
-// count <= 32 fp32 copies in one launch (grid.x sized by the largest)
-int rt1_multi_copy(const float* const* src, float* const* dst, const int64_t* n, int count, hipStream_t st) {
+// count <= MC_MAX fp32 copies (acc: adds) in one launch (grid.x sized by the largest)
+static int multi_copy_launch(const float* const* src, float* const* dst, const int64_t* n, int count, bool acc,
+                             hipStream_t st) {
     if (count <= 0) return 0;
     if (count > MC_MAX) return (int)hipErrorInvalidValue;
     CopyList L;
@@ -267,13 +294,24 @@ int rt1_multi_copy(const float* const* src, float* const* dst, const int64_t* n,
     int64_t gx = (mx / 4 + 255) / 256;
     if (gx > 64) gx = 64;
     if (gx < 1) gx = 1;
-    hipLaunchKernelGGL(multi_copy_kernel, dim3((unsigned)gx, count), dim3(256), 0, st, L);
+    if (acc) hipLaunchKernelGGL(multi_copy_kernel<true>, dim3((unsigned)gx, count), dim3(256), 0, st, L);
+    else hipLaunchKernelGGL(multi_copy_kernel<false>, dim3((unsigned)gx, count), dim3(256), 0, st, L);
     return (int)hipGetLastError();
 }
 
-// count <= MC_MAX reduce-copies in one launch: dst[i][e] = sum_k src[i][k * sstride[i] + e] (k < splits[i])
-int rt1_multi_reduce_copy(const float* const* src, float* const* dst, const int64_t* n, const int64_t* sstride,
-                          const int* splits, int count, hipStream_t st) {
+int rt1_multi_copy(const float* const* src, float* const* dst, const int64_t* n, int count, hipStream_t st) {
+    return multi_copy_launch(src, dst, n, count, false, st);
+}
+
+// dst[i][e] += src[i][e]: the accumulating gather of stolen gradients (same grid as the copy)
+int rt1_multi_add(const float* const* src, float* const* dst, const int64_t* n, int count, hipStream_t st) {
+    return multi_copy_launch(src, dst, n, count, true, st);
+}
+
+// count <= MC_MAX reduce-copies in one launch: dst[i][e] = sum_k src[i][k * sstride[i] + e] (k < splits[i]);
+// acc: dst[i][e] = dst[i][e] + that sum
+static int multi_reduce_launch(const float* const* src, float* const* dst, const int64_t* n, const int64_t* sstride,
+                               const int* splits, int count, bool acc, hipStream_t st) {
     if (count <= 0) return 0;
     if (count > MC_MAX) return (int)hipErrorInvalidValue;
     ReduceList L;
@@ -292,8 +330,19 @@ int rt1_multi_reduce_copy(const float* const* src, float* const* dst, const int6
         if (wg > gx) gx = wg;
     }
     if (gx > 256) gx = 256;
-    hipLaunchKernelGGL(multi_reduce_copy_kernel, dim3((unsigned)gx, count), dim3(256), 0, st, L);
+    if (acc) hipLaunchKernelGGL(multi_reduce_copy_kernel<true>, dim3((unsigned)gx, count), dim3(256), 0, st, L);
+    else hipLaunchKernelGGL(multi_reduce_copy_kernel<false>, dim3((unsigned)gx, count), dim3(256), 0, st, L);
     return (int)hipGetLastError();
+}
+
+int rt1_multi_reduce_copy(const float* const* src, float* const* dst, const int64_t* n, const int64_t* sstride,
+                          const int* splits, int count, hipStream_t st) {
+    return multi_reduce_launch(src, dst, n, sstride, splits, count, false, st);
+}
+
+int rt1_multi_reduce_add(const float* const* src, float* const* dst, const int64_t* n, const int64_t* sstride,
+                         const int* splits, int count, hipStream_t st) {
+    return multi_reduce_launch(src, dst, n, sstride, splits, count, true, st);
 }
 
 }  // extern "C"

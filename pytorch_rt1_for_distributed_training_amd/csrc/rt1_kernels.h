@@ -240,6 +240,10 @@ int rt1_colsum_chunks(int64_t R, int C, int B);
 int rt1_multi_copy(const float* const* src, float* const* dst, const int64_t* n, int count, hipStream_t st);
 int rt1_multi_reduce_copy(const float* const* src, float* const* dst, const int64_t* n, const int64_t* sstride,
                           const int* splits, int count, hipStream_t st);
+// the accumulating forms (gradient accumulation): dst[i] += src[i]; dst[i] = dst[i] + the same fixed-order split sum
+int rt1_multi_add(const float* const* src, float* const* dst, const int64_t* n, int count, hipStream_t st);
+int rt1_multi_reduce_add(const float* const* src, float* const* dst, const int64_t* n, const int64_t* sstride,
+                         const int* splits, int count, hipStream_t st);
 int rt1_colsum(const void* in, int in_is_bf16, int64_t R, int C, int B, float* out, float* tmp, int chunks,
                hipStream_t st);
 

@@ -29,6 +29,14 @@ fused Adam scales the gradient or leaves a non-finite step untouched, and ``buff
 statistics of such a step back -- all inside the captured graph, with no host read.  The norm's summation order
 depends only on the buffer length, so every rank takes the same decision without another collective.
 
+``accumulate_grad_batches=k`` (Lightning's name; 1 = off, and then nothing here changes): ``train_step`` runs one
+micro-batch -- release the gradients, forward, backward, ACCUMULATING gather into the flat gradient -- and the optimizer
+runs on the k-th with ``grad_scale / k``, so the update uses the mean gradient over micro-batches and ranks.  The
+window starts with the one memset of the flat gradient.  With ``graph=True`` the captured graph is the micro-step
+(no memset, no optimizer); the memset and the optimizer / clip / guard launches run eagerly around the replays.  Under
+data parallelism only the final micro-batch all-reduces.  BN running statistics advance once per micro-batch; their
+shadow is the state before the window, so a skipped window rolls all of it back.
+
 No ``network_state`` is fabricated (the reference samples a random one on the
 CPU and copies it to the GPU every step only to read its shape).
 """
@@ -114,7 +122,10 @@ class TrainEngine:
                  gamma: float = 0.1, weight_decay: float = 0.0, bucket_cap_mb: float = 32.0,
                  broadcast_buffers: bool = True, device: Optional[torch.device] = None,
                  grad_comm_dtype: torch.dtype = torch.float32, order_probe: bool = True, comm: str = "torch",
-                 graph: bool = False, max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False):
+                 graph: bool = False, max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False,
+                 accumulate_grad_batches: int = 1):
+        if int(accumulate_grad_batches) != accumulate_grad_batches or accumulate_grad_batches < 1:
+            raise ValueError(f"accumulate_grad_batches must be an integer >= 1, got {accumulate_grad_batches!r}")
         ctx = pdist.context()
         self.cfg = cfg
         self.device = device or pdist.default_device()
@@ -165,7 +176,13 @@ class TrainEngine:
             if self._bn_flat is not None:
                 self._bn_shadow = self._bn_flat.clone()
         self.scheduler = multistep_lr(self.optimizer, list(milestones), gamma)
-        self.global_step = 0
+        self.global_step = 0       # optimizer steps (Lightning's meaning), not micro-batches
+        # gradient accumulation: micro_step = micro-batches already in the open window, stepped = whether the last
+        # train_step applied the optimizer (always, without accumulation)
+        self.accumulate_grad_batches = int(accumulate_grad_batches)
+        self.micro_step = 0
+        self.stepped = True
+        self.ddp.accumulate = self.accumulate_grad_batches > 1
         # one GPU: the whole step is one graph; data parallel: forward+backward is the graph, the gradient
         # all-reduce and Adam run after each replay (collectives are never captured)
         self.graph = bool(graph) and self.backend == "hip" and self.device.type == "cuda"
@@ -248,6 +265,8 @@ class TrainEngine:
         return loss.detach()
 
     def train_step(self, batch: Dict) -> torch.Tensor:
+        if self.accumulate_grad_batches > 1:
+            return self._accum_step(batch)
         if self.graph and self._static_batch is not None and not _same_shapes(self._static_batch, batch):
             # a batch of another shape (e.g. a short last batch) cannot replay the captured graph: run it eagerly
             loss = self._step_body(batch)
@@ -262,6 +281,86 @@ class TrainEngine:
         self.global_step += 1
         return loss
 
+    # ------------------------------------------------------------------ gradient accumulation (k > 1)
+    def _window_begin(self):
+        self.flat.grad.zero_()
+        if "nosync" in _DP_DIAG and self._segments is not None:
+            self.ddp.reset_buckets()                 # diagnostic, as in _graph_dp_step: no BN-buffer broadcast
+        else:
+            self.ddp.prepare()                       # bucket counters, one BN-buffer broadcast per window
+
+    def _window_end(self):
+        """Optimizer on the accumulated (and, under DP, all-reduced) gradient of ``micro_step`` micro-batches."""
+        self.optimizer.step(grad_scale=self.ddp.grad_scale / self.micro_step)
+        self._guard_buffers()
+        self.micro_step = 0
+        self.global_step += 1
+        self.stepped = True
+
+    def _micro_body(self, batch: Dict) -> torch.Tensor:
+        """Release, forward, backward, accumulating gather: what the one-GPU micro-step graph holds."""
+        self.model.train()
+        self.flat.release_grads()
+        loss, _ = self.forward_loss(batch)
+        with deferred_sums(self._defer_sums):
+            loss.backward()
+        self.ddp.finish()
+        return loss.detach()
+
+    def _eager_micro_step(self, batch: Dict) -> torch.Tensor:
+        if self.micro_step == 0:
+            self._window_begin()
+        else:
+            # the window's earlier micro-batches may have left the bucket counters anywhere (a segmented capture
+            # marks every bucket launched; so does a replayed or dropped graph's window): this backward's hooks
+            # must find them fresh, or a final micro-batch would gather and never all-reduce
+            self.ddp.reset_buckets()
+        final = self.micro_step + 1 == self.accumulate_grad_batches
+        # a non-final micro-batch launches no bucket and gathers its whole gradient at the end of the backward
+        with contextlib.nullcontext() if final else self.ddp.no_sync():
+            loss = self._micro_body(batch)
+        self.micro_step += 1
+        if final:
+            self._window_end()
+        return loss
+
+    def _accum_step(self, batch: Dict) -> torch.Tensor:
+        self.stepped = False
+        if not self.graph or (self._static_batch is not None and not _same_shapes(self._static_batch, batch)):
+            return self._eager_micro_step(batch)
+        dp = self.ddp.enabled
+        if (self._segments if dp else self._graph) is None:
+            loss = self._eager_micro_step(batch)     # real micro-step, also warms up lazily-initialised state
+            if dp:
+                self._capture_dp_collectively(batch)
+            else:
+                try:
+                    self._capture(batch)
+                except Exception as e:
+                    self._capture_failed(e)
+            return loss
+        if self.micro_step == 0:
+            self._window_begin()
+        final = self.micro_step + 1 == self.accumulate_grad_batches
+        _copy_into(self._static_batch, batch)
+        if not dp:
+            self._graph.replay()
+        else:
+            self._replay_segments(launch=final)      # only the final micro-batch all-reduces its buckets
+        self.micro_step += 1
+        if final:
+            self._window_end()
+        return self._static_loss.clone()
+
+    def flush_window(self) -> bool:
+        """Apply a partial accumulation window (an epoch ended inside it): the optimizer runs on the mean of the
+        ``micro_step`` micro-batches gathered so far.  No-op (False) on an empty window."""
+        if self.accumulate_grad_batches <= 1 or self.micro_step == 0:
+            return False
+        self.ddp.all_reduce_grads()                  # none of these micro-batches was the window's final one
+        self._window_end()
+        return True
+
     # ------------------------------------------------------------------ hipGraph step
     def _graph_step(self, batch: Dict) -> torch.Tensor:
         if self._graph is None:
@@ -270,11 +369,7 @@ class TrainEngine:
             try:
                 self._capture(batch)
             except Exception as e:   # capture is an optimisation: never lose the run to it
-                import sys
-                print(f"[rt1] hipGraph capture failed ({type(e).__name__}: {e}); continuing eagerly",
-                      file=sys.stderr, flush=True)
-                self.graph = False
-                self._graph = None
+                self._capture_failed(e)
             return loss
         _copy_into(self._static_batch, batch)
         opt = self.optimizer
@@ -286,6 +381,13 @@ class TrainEngine:
         self.global_step += 1
         return self._static_loss.clone()
 
+    def _capture_failed(self, e: Exception):
+        import sys
+        print(f"[rt1] hipGraph capture failed ({type(e).__name__}: {e}); continuing eagerly",
+              file=sys.stderr, flush=True)
+        self.graph = False
+        self._graph = None
+
     def _capture(self, batch: Dict):
         self._static_batch = _clone_tree(batch)
         torch.cuda.synchronize(self.device)
@@ -294,7 +396,10 @@ class TrainEngine:
         steps_before = self.optimizer.step_count
         try:
             with torch.cuda.graph(g, capture_error_mode="relaxed" if "relaxed1" in _DP_DIAG else "global"):
-                self._static_loss = self._step_body(self._static_batch)
+                if self.accumulate_grad_batches > 1:
+                    self._static_loss = self._micro_body(self._static_batch)     # no memset, no optimizer
+                else:
+                    self._static_loss = self._step_body(self._static_batch)
         finally:
             # the capture recorded the step; it did not run it (restore even when the capture failed, so an eager
             # fallback continues from the right Adam step and re-syncs the device copy)
@@ -308,26 +413,24 @@ class TrainEngine:
         if self._segments is None:
             loss = self._step_body(batch)            # eager step (bucketed, overlapped DP) warms everything up
             self.global_step += 1
-            err = None
-            try:
-                _test_capture_failure()
-                self._capture_segments(batch)
-            except Exception as e:
-                err = e
-            # capture success is a COLLECTIVE decision: a rank whose capture failed runs eager steps, whose bucket
-            # all-reduces are issued from hooks in a different order and count than the graph-DP replay's, so every
-            # rank must take the same path or the collectives stop lining up (summing buckets of different steps, or
-            # hanging).  No collective runs during the capture itself, so every rank reaches this all-reduce.
-            if not pdist.all_true(err is None):
-                import sys
-                why = f"{type(err).__name__}: {err}" if err is not None else "failed on another rank"
-                print(f"[rt1] segmented hipGraph capture {why}; every rank continues eagerly", file=sys.stderr,
-                      flush=True)
-                self.drop_graph()
+            self._capture_dp_collectively(batch)
             return loss
         _copy_into(self._static_batch, batch)
         if "nosync" not in _DP_DIAG:
             self.ddp.sync_buffers()                  # rank-0 BN buffers before the forward (DDP parity)
+        self._replay_segments()
+        self.optimizer.step(grad_scale=self.ddp.grad_scale)
+        self._guard_buffers()
+        self.global_step += 1
+        return self._static_loss.clone()
+
+    def _replay_segments(self, launch: bool = True):
+        """Replay the captured segments, issuing each completed bucket's all-reduce between them, and wait for all of
+        them.  ``launch=False`` (a non-final micro-batch of an accumulation window): replay only, no collective and
+        no comm-timing record (``comm_timing`` / ``bucket_timing`` hold one entry per replay that all-reduced)."""
+        if not launch:
+            self._segments.replay_with(lambda buckets: None)
+            return
         works = []
         timing = self.comm_timing is not None
         launched = []                                # (bucket indices, event after the segment that completed them)
@@ -370,10 +473,24 @@ class TrainEngine:
             self.bucket_timing.append(per_bucket)
         else:
             self.ddp.wait_all(works)
-        self.optimizer.step(grad_scale=self.ddp.grad_scale)
-        self._guard_buffers()
-        self.global_step += 1
-        return self._static_loss.clone()
+
+    def _capture_dp_collectively(self, batch: Dict):
+        err = None
+        try:
+            _test_capture_failure()
+            self._capture_segments(batch)
+        except Exception as e:
+            err = e
+        # capture success is a COLLECTIVE decision: a rank whose capture failed runs eager steps, whose bucket
+        # all-reduces are issued from hooks in a different order and count than the graph-DP replay's, so every
+        # rank must take the same path or the collectives stop lining up (summing buckets of different steps, or
+        # hanging).  No collective runs during the capture itself, so every rank reaches this all-reduce.
+        if not pdist.all_true(err is None):
+            import sys
+            why = f"{type(err).__name__}: {err}" if err is not None else "failed on another rank"
+            print(f"[rt1] segmented hipGraph capture {why}; every rank continues eagerly", file=sys.stderr,
+                  flush=True)
+            self.drop_graph()
 
     def _capture_segments(self, batch: Dict):
         from .graphs import SegmentedCapture
@@ -393,13 +510,17 @@ class TrainEngine:
             with torch.cuda.stream(side):
                 seg.begin()
                 self.model.train()
-                self.optimizer.zero_grad()
+                if self.accumulate_grad_batches > 1:
+                    self.flat.release_grads()        # the window's memset stays outside the segments
+                else:
+                    self.optimizer.zero_grad()
                 with self.ddp.capture_cuts(seg):
                     loss, _ = self.forward_loss(self._static_batch)
                     with deferred_sums(self._defer_sums):
                         loss.backward()
                 rest = self.ddp.unlaunched_buckets()
-                self.flat.gather_grads()             # buckets that never completed (a param without a gradient)
+                # buckets that never completed (a param without a gradient)
+                self.flat.gather_grads(accumulate=self.ddp.accumulate)
                 self._static_loss = loss.detach()
                 seg.end(extra_buckets=rest)
         except BaseException:
@@ -441,7 +562,10 @@ class TrainEngine:
                         cpu_rng=torch.get_rng_state(),
                         ctr={d: t.clone() for d, t in _rng._COUNTERS.items()}, gstep=self.global_step,
                         clip=(opt.clip_state.clone() if opt.clip_state is not None else None),
-                        shadow=(self._bn_shadow.clone() if self._bn_shadow is not None else None))
+                        shadow=(self._bn_shadow.clone() if self._bn_shadow is not None else None),
+                        # an open accumulation window is state too: what it gathered so far and its position
+                        grad=(self.flat.grad.clone() if self.accumulate_grad_batches > 1 else None),
+                        micro=self.micro_step, stepped=self.stepped)
 
     def _restore(self, s: Dict):
         from ..ops import rng as _rng
@@ -459,6 +583,9 @@ class TrainEngine:
                 opt.clip_state.copy_(s["clip"])
             if s["shadow"] is not None:
                 self._bn_shadow.copy_(s["shadow"])
+            if s["grad"] is not None:
+                self.flat.grad.copy_(s["grad"])
+        self.micro_step, self.stepped = s["micro"], s["stepped"]
         opt.step_count, opt._dev_step, opt._dev_lr = s["step"], s["dev_step"], s["dev_lr"]
         if s["rng"] is not None:
             torch.cuda.set_rng_state(s["rng"], self.device)
@@ -469,7 +596,9 @@ class TrainEngine:
         """One captured-graph step and one eager step on ``batch`` from the SAME state (parameters, Adam moments, BN
         running statistics, RNG states, dropout counter); the reduced flat gradients, the updated parameters and the
         losses must be bitwise equal (every kernel is deterministic and the random draws replay identically).  The
-        engine is left in the pre-check state.  None when no graph has been captured (nothing to compare)."""
+        engine is left in the pre-check state.  None when no graph has been captured (nothing to compare).
+        With ``accumulate_grad_batches > 1`` the two are one replayed and one eager MICRO-step from the same state,
+        the flat gradient gathered so far and the window position included."""
         if not self.graph or (self._graph is None and self._segments is None):
             return None
         if not _same_shapes(self._static_batch, batch):
@@ -484,7 +613,7 @@ class TrainEngine:
                 torch.cuda.synchronize(self.device)
             grad_g, data_g = self.flat.grad.clone(), self.flat.data.clone()
             self._restore(snap)
-            loss_e = self._step_body(batch)
+            loss_e = (self._eager_micro_step(batch) if self.accumulate_grad_batches > 1 else self._step_body(batch))
             if self.device.type == "cuda":
                 torch.cuda.synchronize(self.device)
             res = dict(grads=bool(torch.equal(grad_g, self.flat.grad)),

@@ -19,6 +19,11 @@ instead: the loss means are taken over the finite steps, ``grad_norm`` /
 ``clipped_steps`` / ``skipped_steps`` are logged at each log interval, and the
 run aborts only when a whole log window (at least ``MIN_SKIPS_TO_ABORT``
 consecutive steps) was skipped.
+
+With the engine's ``accumulate_grad_batches=k`` a ``train_step`` is one micro-batch: steps, log points and
+``global_step`` count optimizer steps (as Lightning does), ``train_loss_step`` is the mean over the micro-batches of
+the logged windows, and a window left open when an epoch's batches run out is applied (``engine.flush_window``) before
+validation, the LR scheduler and checkpointing, so no checkpoint ever holds a half-accumulated gradient.
 """
 from __future__ import annotations
 
@@ -170,6 +175,7 @@ class Trainer:
                 train_loader.set_epoch(epoch)
             self._log({"lr-Adam": e.lr})
             total, n, window, wn = None, 0, None, 0
+            wsteps = 0                               # optimizer steps since the last log point (wn counts batches)
             samples = 0
             opt = e.optimizer
             clip_on = bool(getattr(opt, "clip_enabled", False))
@@ -177,6 +183,34 @@ class Trainer:
             # skip_nonfinite: means over the finite-loss steps only (device-side masked sums and counts, no sync)
             tcount = wcount = None
             t0 = time.perf_counter()
+
+            def log_point():
+                # after a train_step (or the epoch-end flush) that applied the optimizer
+                nonlocal window, wn, wcount, wsteps
+                wsteps += 1
+                if e.global_step % self.log_every == 0:
+                    step_loss = self._mean_across(window, wcount if skip_on else wn)
+                    if skip_on:
+                        # a skipped step is survived, a dead run is not: every step of this window skipped
+                        # (MIN_SKIPS_TO_ABORT: a one-step window cannot tell the two apart)
+                        streak = int(opt.clip_state[5])
+                        if streak >= max(wsteps, MIN_SKIPS_TO_ABORT):
+                            raise NonFiniteLoss(f"{streak} consecutive non-finite steps skipped up to step "
+                                                f"{e.global_step}")
+                    elif not math.isfinite(step_loss):
+                        raise NonFiniteLoss(f"non-finite train loss at step {e.global_step}: {step_loss}")
+                    metrics = {"train_loss_step": step_loss} if math.isfinite(step_loss) else {}
+                    if clip_on:
+                        metrics.update(grad_norm=float(opt.last_grad_norm), clipped_steps=opt.clipped_steps,
+                                       skipped_steps=opt.skipped_steps)
+                    self._log(metrics)
+                    window, wn, wcount, wsteps = None, 0, None, 0
+                    if self.verbose:
+                        extra = (f" grad_norm {metrics['grad_norm']:.4g} clipped {metrics['clipped_steps']} "
+                                 f"skipped {metrics['skipped_steps']}") if clip_on else ""
+                        print(f"epoch {epoch} step {e.global_step} train_loss {step_loss:.6f} lr {e.lr:.2e}{extra}",
+                              flush=True)
+
             for batch in self._iter(train_loader, self.limit_train):
                 loss = e.train_step(batch)
                 if e.graph and not self.graph_checked and (e._graph is not None or e._segments is not None):
@@ -192,28 +226,10 @@ class Trainer:
                 n += 1
                 wn += 1
                 samples += int(batch["action_label"]["action"].shape[0]) * pdist.context().world_size
-                if e.global_step % self.log_every == 0:
-                    step_loss = self._mean_across(window, wcount if skip_on else wn)
-                    if skip_on:
-                        # a skipped step is survived, a dead run is not: every step of this window skipped
-                        # (MIN_SKIPS_TO_ABORT: a one-step window cannot tell the two apart)
-                        streak = int(opt.clip_state[5])
-                        if streak >= max(wn, MIN_SKIPS_TO_ABORT):
-                            raise NonFiniteLoss(f"{streak} consecutive non-finite steps skipped up to step "
-                                                f"{e.global_step}")
-                    elif not math.isfinite(step_loss):
-                        raise NonFiniteLoss(f"non-finite train loss at step {e.global_step}: {step_loss}")
-                    metrics = {"train_loss_step": step_loss} if math.isfinite(step_loss) else {}
-                    if clip_on:
-                        metrics.update(grad_norm=float(opt.last_grad_norm), clipped_steps=opt.clipped_steps,
-                                       skipped_steps=opt.skipped_steps)
-                    self._log(metrics)
-                    window, wn, wcount = None, 0, None
-                    if self.verbose:
-                        extra = (f" grad_norm {metrics['grad_norm']:.4g} clipped {metrics['clipped_steps']} "
-                                 f"skipped {metrics['skipped_steps']}") if clip_on else ""
-                        print(f"epoch {epoch} step {e.global_step} train_loss {step_loss:.6f} lr {e.lr:.2e}{extra}",
-                              flush=True)
+                if e.stepped:
+                    log_point()
+            if e.flush_window():                     # a partial accumulation window: one more optimizer step
+                log_point()
             if e.device.type == "cuda":
                 torch.cuda.synchronize()
             dt = time.perf_counter() - t0

@@ -72,6 +72,10 @@ class DataParallel:
         self.broadcast_buffers = broadcast_buffers and self.enabled
         self.grad_comm_dtype = grad_comm_dtype
         self._sync = True
+        # gradient accumulation (TrainEngine(accumulate_grad_batches > 1)): every gather adds to the flat gradient; a
+        # non-final micro-batch runs under no_sync() and lands its whole gradient in finish(), the final one
+        # all-reduces each bucket's accumulated slice from the hooks as usual
+        self.accumulate = False
         self.launch_log: List[int] = []   # bucket indices in the order their all-reduce was issued (last step)
         self._capture = None   # SegmentedCapture while a hipGraph DP step is being captured (engine/graphs.py)
         self.buffers = flatten_buffers(module) if self.enabled else None
@@ -139,7 +143,7 @@ class DataParallel:
                     b.launched = True
                     if self.flat.grad.is_cuda and torch.cuda.current_stream() != self._capture.stream:
                         raise RuntimeError("gradient hook ran off the capture stream; segmented capture impossible")
-                    self.flat.gather_grads(b.members)
+                    self.flat.gather_grads(b.members, accumulate=self.accumulate)
                     self._capture.bucket_ready(b.index)
                 return
             if not self._sync:
@@ -153,7 +157,7 @@ class DataParallel:
     def _launch(self, b: _Bucket):
         b.launched = True
         self.launch_log.append(b.index)
-        self.flat.gather_grads(b.members)
+        self.flat.gather_grads(b.members, accumulate=self.accumulate)
         b.work = self._all_reduce(self.flat.grad[b.start:b.end])
         if _DEBUG_SYNC_LAUNCH:      # debug: no overlap of a bucket's all-reduce with the rest of the backward
             b.work.wait()
@@ -161,21 +165,27 @@ class DataParallel:
             b.work = None
 
     # ------------------------------------------------------------------ step protocol
-    def prepare(self):
-        """Call before forward: reset bucket state, broadcast BN buffers."""
+    def reset_buckets(self):
+        """Bucket counters back to 'nothing arrived, nothing launched' (no collective).  Before every backward whose
+        hooks launch buckets: the step's ``prepare()``, and each later micro-batch of an accumulation window (a
+        segmented capture in between leaves every bucket marked launched)."""
         for b in self.buckets:
             b.pending = len(b.members)
             b.launched = False
             b.work = None
         self.launch_log = []
+
+    def prepare(self):
+        """Call before forward: reset bucket state, broadcast BN buffers."""
+        self.reset_buckets()
         if self._sync:
             self.sync_buffers()
 
     def finish(self):
         """Call after backward: flush incomplete buckets and wait (stream-wise) for all."""
         if not self.enabled or not self._sync:
-            if self._sync:
-                self.flat.gather_grads()
+            if self._sync or self.accumulate:
+                self.flat.gather_grads(accumulate=self.accumulate)
             return
         for b in self.buckets:
             if not b.launched:
@@ -184,7 +194,8 @@ class DataParallel:
             if b.work is not None:
                 b.work.wait()
                 b.work = None
-        self.flat.gather_grads()   # clears the 'loose' flag (every bucket already gathered its members)
+        # clears the 'loose' flag (every bucket already gathered its members)
+        self.flat.gather_grads(accumulate=self.accumulate)
 
     def all_reduce_grads(self):
         """Sum the whole (already gathered) flat gradient across ranks, bucket by bucket, all in flight at once,

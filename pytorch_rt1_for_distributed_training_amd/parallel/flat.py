@@ -54,8 +54,11 @@ DEFER_MAX_BYTES = 24 << 20
 
 class deferred_sums:
     """Context of one backward whose parameter gradients the flat gather collects: weight-gradient sites may return
-    unsummed split partials (``defer_partials``).  Not for gradient accumulation over several backwards (a second
-    backward's AccumulateGrad would add only its first split)."""
+    unsummed split partials (``defer_partials``).  Every such backward must be followed by a gather before the next
+    one starts.  Gradient accumulation over several backwards is supported in exactly that form: release the
+    gradients (``FlatParameters.release_grads``), run the backward, then ``gather_grads(accumulate=True)``, which adds
+    each fixed-order split sum to the flat buffer.  What is not supported is a second backward into the same
+    ``.grad`` tensors (AccumulateGrad would add only the first split); the accumulating gather raises on it."""
 
     def __init__(self, enabled: bool = True):
         self.enabled = enabled
@@ -111,9 +114,11 @@ def _pending_of(g: torch.Tensor):
     return base, ent[0].shape[0], ent[0][0].numel()
 
 
-def _copy_many(dst: List[torch.Tensor], src: List[torch.Tensor]):
-    """dst[i].copy_(src[i]): on the GPU through the extension's multi-copy kernel (32 tensors per launch instead of
-    one blit per tensor), else ``torch._foreach_copy_``."""
+def _land_many(dst: List[torch.Tensor], src: List[torch.Tensor], accumulate: bool = False):
+    """Land stolen gradients ``src`` in their flat views ``dst``: dst[i].copy_(src[i]) on the GPU through the
+    extension's multi-copy kernel (128 tensors per launch instead of one blit per tensor), else
+    ``torch._foreach_copy_``.  ``accumulate``: dst[i] += src[i] instead (``multi_add_``, else ``torch._foreach_add_``)."""
+    each = torch._foreach_add_ if accumulate else torch._foreach_copy_
     if dst[0].is_cuda and MULTI_COPY:
         from ..ops import available, load
         if available():
@@ -121,12 +126,13 @@ def _copy_many(dst: List[torch.Tensor], src: List[torch.Tensor]):
                   for d, s in zip(dst, src)]
             fast = [i for i, k in enumerate(ok) if k]
             if fast:
-                load().multi_copy_([dst[i] for i in fast], [src[i] for i in fast])
+                many = load().multi_add_ if accumulate else load().multi_copy_
+                many([dst[i] for i in fast], [src[i] for i in fast])
             rest = [i for i, k in enumerate(ok) if not k]
             if rest:
-                torch._foreach_copy_([dst[i] for i in rest], [src[i] for i in rest])
+                each([dst[i] for i in rest], [src[i] for i in rest])
             return
-    torch._foreach_copy_(dst, src)
+    each(dst, src)
 
 
 class FlatParameters:
@@ -154,6 +160,7 @@ class FlatParameters:
         self.index: Dict[int, int] = {id(p): i for i, p in enumerate(params)}
         self.views: List[torch.Tensor] = [p.grad for p in params]
         self._loose = False   # some .grad may not be a flat view (released by zero_grad(set_to_none=True))
+        self._landed = set()  # accumulate mode: parameters already gathered since the last release
 
     def zero_grad(self, set_to_none: bool = False):
         self.grad.zero_()
@@ -161,11 +168,22 @@ class FlatParameters:
             for p in self.params:
                 p.grad = None
             self._loose = True
+            self._landed.clear()
 
-    def gather_grads(self, indices: Optional[Sequence[int]] = None):
+    def release_grads(self):
+        """``zero_grad(set_to_none=True)`` without the memset: the flat buffer keeps what earlier backwards of an
+        accumulation window gathered, and the next backward's gradients are stolen again (no per-parameter
+        ``grad += g`` launches); land them with ``gather_grads(accumulate=True)``."""
+        for p in self.params:
+            p.grad = None
+        self._loose = True
+        self._landed.clear()
+
+    def gather_grads(self, indices: Optional[Sequence[int]] = None, accumulate: bool = False):
         """Copy gradients that autograd stored outside the flat buffer into it (one ``_foreach_copy_``)
         and point ``.grad`` back at the flat views.  Parameters without a gradient keep the zeros of
-        the last ``zero_grad``."""
+        the last ``zero_grad``.  ``accumulate``: add them to the flat buffer instead (``multi_add_`` /
+        ``multi_reduce_add_``), each parameter once per ``release_grads``."""
         if not self._loose:
             self._check_pending(indices)
             return
@@ -174,6 +192,15 @@ class FlatParameters:
         for i in (range(len(self.params)) if indices is None else indices):
             p, v = self.params[i], self.views[i]
             g = p.grad
+            if accumulate:
+                if i in self._landed:
+                    continue
+                self._landed.add(i)
+                if g is not None and g.numel() and g.data_ptr() == v.data_ptr():
+                    # autograd added a second backward into the flat view in place (for a deferred split-K gradient:
+                    # only its first split); adding the view to itself would count it twice
+                    raise RuntimeError("accumulating gather found a gradient that already is its flat view: release "
+                                       "the gradients (release_grads) before every backward of an accumulation window")
             if g is not None and g.data_ptr() != v.data_ptr():
                 pend = _pending_of(g) if g.is_cuda else None
                 if pend is not None:
@@ -188,10 +215,11 @@ class FlatParameters:
             p.grad = v
         if red:
             from ..ops import load
-            load().multi_reduce_copy_([r[0] for r in red], [r[1] for r in red], [r[2] for r in red],
-                                      [r[3] for r in red])
+            ext = load()
+            (ext.multi_reduce_add_ if accumulate else ext.multi_reduce_copy_)(
+                [r[0] for r in red], [r[1] for r in red], [r[2] for r in red], [r[3] for r in red])
         if dst:
-            _copy_many(dst, src)
+            _land_many(dst, src, accumulate)
         for b in used:
             if _PENDING[b][2] <= 0:
                 del _PENDING[b]
