@@ -64,6 +64,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--accumulate_grad_batches", type=int, default=1,
                    help="optimizer step every N batches on the mean of their gradients (Lightning's name; N x "
                         "--batch_size on one GPU computes the mean gradient of N data-parallel ranks)")
+    p.add_argument("--ema_decay", type=float, default=0.0,
+                   help="exponential moving average of the trainable weights, updated inside the fused Adam launch "
+                        "(0 = off; 0.999-0.9999 is usual); validation also logs eval_loss_ema, checkpoints carry the "
+                        "average under 'ema', eval_rt1.py --ema evaluates it")
+    p.add_argument("--no_ema_warmup", action="store_true",
+                   help="use --ema_decay from the first step instead of min(decay, (1 + t) / (10 + t))")
     p.add_argument("--bucket_cap_mb", type=float, default=32.0)
     p.add_argument("--no_broadcast_buffers", action="store_true")
     p.add_argument("--comm", choices=["torch", "native"], default="torch",
@@ -211,11 +217,14 @@ def train(args):
                          comm=args.comm, graph=use_graph,
                          max_grad_norm=args.gradient_clip_val if args.gradient_clip_val > 0 else None,
                          skip_nonfinite=args.skip_nonfinite_steps,
-                         accumulate_grad_batches=args.accumulate_grad_batches)
+                         accumulate_grad_batches=args.accumulate_grad_batches, ema_decay=args.ema_decay,
+                         ema_warmup=not args.no_ema_warmup)
     if ctx.is_main:
         print(f"[train] gradient_clip_val {args.gradient_clip_val if args.gradient_clip_val > 0 else 'off'}, "
               f"skip_nonfinite_steps {'on' if args.skip_nonfinite_steps else 'off'}, "
               f"accumulate_grad_batches {args.accumulate_grad_batches}", flush=True)
+        if args.ema_decay > 0:
+            print(f"[train] ema_decay {args.ema_decay} (warm-up {'off' if args.no_ema_warmup else 'on'})", flush=True)
     ckpt = ModelCheckpoint(os.path.join(args.ckpt_dir, args.exp_name), every_n_epochs=args.ckpt_every_n_epochs)
     loggers = []
     if ctx.is_main:

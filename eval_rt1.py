@@ -33,6 +33,8 @@ def main(argv=None):
     ap.add_argument("--device", default=None)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--no_video", action="store_true")
+    ap.add_argument("--ema", action="store_true",
+                    help="evaluate the checkpoint's averaged weights (written when training ran with --ema_decay)")
     a = ap.parse_args(argv)
 
     import torch
@@ -42,7 +44,7 @@ def main(argv=None):
     torch.manual_seed(a.seed)
     device = a.device or ("cuda" if torch.cuda.is_available() else "cpu")
     cfg = RT1Config(height=a.height, width=a.width, seq_len=a.seq_len, num_layers=a.num_layers)
-    policy = RT1Policy.from_checkpoint(a.ckpt, cfg, device=device)
+    policy = RT1Policy.from_checkpoint(a.ckpt, cfg, device=device, use_ema=a.ema)
     if a.env == "sim":
         env = make_sim_env(a.reward, a.block_mode, seed=a.seed, reject_unsolvable=not a.no_reject)
     elif a.env == "toy":

@@ -160,6 +160,51 @@ void flat_adam_clip_dev(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v, 
                  "flat_adam_clip_dev");
 }
 
+bool overlaps(const at::Tensor& a, const at::Tensor& b) {
+    const char* a0 = static_cast<const char*>(a.data_ptr());
+    const char* b0 = static_cast<const char*>(b.data_ptr());
+    return a0 < b0 + b.nbytes() && b0 < a0 + a.nbytes();
+}
+
+// fused Adam + exponential moving average of the weights; clip_state = None: the plain form, else the clip form
+void flat_adam_ema_dev(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v, at::Tensor ema, at::Tensor state,
+                       at::Tensor ema_state, const OptT& clip_state, double beta1, double beta2, double eps,
+                       double weight_decay, double grad_scale, double one_minus_decay, bool warmup) {
+    check_dev(p, "param", at::kFloat);
+    check_dev(g, "grad", at::kFloat);
+    check_dev(m, "exp_avg", at::kFloat);
+    check_dev(v, "exp_avg_sq", at::kFloat);
+    check_dev(ema, "ema", at::kFloat);
+    check_dev(state, "state", at::kFloat);
+    check_dev(ema_state, "ema_state", at::kFloat);
+    const float* cs = nullptr;
+    if (clip_state.has_value() && clip_state->defined()) {
+        check_clip_state(*clip_state, "flat_adam_ema_dev");
+        TORCH_CHECK(clip_state->device() == p.device(), "flat_adam_ema_dev: clip_state on another device");
+        cs = clip_state->data_ptr<float>();
+    }
+    const int64_t n = p.numel();
+    TORCH_CHECK(g.numel() == n && m.numel() == n && v.numel() == n && ema.numel() == n && state.numel() >= 2,
+                "flat_adam_ema_dev: sizes");
+    TORCH_CHECK(ema_state.numel() >= 4 && aligned16(ema_state),
+                "flat_adam_ema_dev: ema_state must be fp32[4], 16-byte aligned");
+    TORCH_CHECK(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) && aligned16(ema),
+                "flat_adam_ema_dev: buffers must be 16-byte aligned");
+    TORCH_CHECK(g.device() == p.device() && m.device() == p.device() && v.device() == p.device() &&
+                ema.device() == p.device() && state.device() == p.device() && ema_state.device() == p.device(),
+                "flat_adam_ema_dev: tensors on different devices");
+    TORCH_CHECK(!overlaps(ema, p) && !overlaps(ema, g) && !overlaps(ema, m) && !overlaps(ema, v) &&
+                !overlaps(ema_state, state) && !overlaps(ema_state, ema),
+                "flat_adam_ema_dev: ema / ema_state must not alias another buffer");
+    TORCH_CHECK(one_minus_decay > 0.0 && one_minus_decay <= 1.0, "flat_adam_ema_dev: one_minus_decay must be in (0, 1]");
+    check_launch(rt1_flat_adam_ema_dev(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(),
+                                       v.data_ptr<float>(), ema.data_ptr<float>(), n, state.data_ptr<float>(), cs,
+                                       ema_state.data_ptr<float>(), (float)beta1, (float)beta2, (float)eps,
+                                       (float)weight_decay, (float)grad_scale, (float)one_minus_decay, warmup ? 1 : 0,
+                                       cur_stream()),
+                 "flat_adam_ema_dev");
+}
+
 // Deterministic fixed-order sum over the rows of B x [R, C] (fp32 or bf16, contiguous) -> B x [C] fp32
 // (csrc/kernels/reduce.hip).  Replaces ATen's tall-reduction path, whose cross-workgroup semaphore combine gave
 // wrong weight gradients under hipGraph replay.
@@ -1489,6 +1534,7 @@ PYBIND11_MODULE(_rt1_hip, m) {
     m.def("flat_adam", &flat_adam, "fused Adam/AdamW over flat fp32 buffers");
     m.def("flat_adam_dev", &flat_adam_dev, "fused Adam/AdamW, step/lr read from a device tensor (graph-replayable)");
     m.def("flat_adam_clip_dev", &flat_adam_clip_dev, "flat_adam_dev obeying clip_state (clip coefficient, skipped step)");
+    m.def("flat_adam_ema_dev", &flat_adam_ema_dev, "flat_adam_dev / flat_adam_clip_dev that also updates the EMA of the weights");
     m.def("gradnorm_partials", &gradnorm_partials, "fp64 partial sums grad_sumsq writes for n floats");
     m.def("grad_sumsq", &grad_sumsq, "deterministic sum of squares of a flat fp32 gradient -> fp64 partials");
     m.def("grad_clip_finalize", &grad_clip_finalize, "partials -> clip_state {norm, coef, ok, counters}");

@@ -101,7 +101,85 @@ __global__ __launch_bounds__(256) void flat_adam_clip_kernel(float* __restrict__
     }
 }
 
+// The device-state update that also carries an exponential moving average of the weights: per float4 it loads
+// p, g, m, v, ema, runs adam_elem exactly as flat_adam_kernel (CLIP = false) or flat_adam_clip_kernel (CLIP = true)
+// do -- p, m, v come out bit for bit the same -- then ema = fma(omd_t, p_new - ema, ema) and stores p, m, v, ema
+// (36 B/elem instead of 28).  omd is one minus the decay; with warm-up omd_t = max(omd, 9 / (10 + t)), i.e. the decay
+// min(decay, (1 + t) / (10 + t)), where t is the Adam step this call performs (the t of the bias corrections, read on
+// the device, so a replayed graph advances it).  A skipped step leaves before its first load and writes nothing.
+// Lane 0 of workgroup 0 records {omd_t, t, 0, 0} in ema_state with one ordinary vector store.
+template <bool CLIP>
+__device__ __forceinline__ float pre_scale(float g, float gs) { return CLIP ? g * gs : g; }
+
+template <bool CLIP>
+__global__ __launch_bounds__(256) void flat_adam_ema_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                            float* __restrict__ m, float* __restrict__ v,
+                                                            float* __restrict__ ema, int64_t n4, int64_t n, AdamArgs a,
+                                                            const float* __restrict__ state,
+                                                            const float* __restrict__ clip_state,
+                                                            float* __restrict__ ema_state, float omd, int warmup) {
+    float gs = 1.f, t = state[0];
+    if (CLIP) {
+        if (clip_state[2] == 0.f) return;
+        gs = a.grad_scale;
+        a.grad_scale = clip_state[1];  // adam_elem's own multiply applies the clip coefficient second
+        t -= clip_state[3];
+    }
+    {
+        const float lr = state[1];
+        a.lr = lr;
+        a.step_size = lr / -expm1f(t * logf(a.beta1));
+        a.inv_sqrt_bc2 = rsqrtf(-expm1f(t * logf(a.beta2)));
+    }
+    const float omd_t = warmup ? fmaxf(omd, 9.f / (10.f + t)) : omd;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *reinterpret_cast<float4*>(ema_state) = make_float4(omd_t, t, 0.f, 0.f);
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    float4* p4 = reinterpret_cast<float4*>(p);
+    const float4* g4 = reinterpret_cast<const float4*>(g);
+    float4* m4 = reinterpret_cast<float4*>(m);
+    float4* v4 = reinterpret_cast<float4*>(v);
+    float4* e4 = reinterpret_cast<float4*>(ema);
+    for (; i < n4; i += stride) {
+        float4 pp = p4[i], gg = g4[i], mm = m4[i], vv = v4[i], ee = e4[i];
+        adam_elem(pp.x, pre_scale<CLIP>(gg.x, gs), mm.x, vv.x, a);
+        adam_elem(pp.y, pre_scale<CLIP>(gg.y, gs), mm.y, vv.y, a);
+        adam_elem(pp.z, pre_scale<CLIP>(gg.z, gs), mm.z, vv.z, a);
+        adam_elem(pp.w, pre_scale<CLIP>(gg.w, gs), mm.w, vv.w, a);
+        ee.x = fmaf(omd_t, pp.x - ee.x, ee.x);
+        ee.y = fmaf(omd_t, pp.y - ee.y, ee.y);
+        ee.z = fmaf(omd_t, pp.z - ee.z, ee.z);
+        ee.w = fmaf(omd_t, pp.w - ee.w, ee.w);
+        p4[i] = pp; m4[i] = mm; v4[i] = vv; e4[i] = ee;
+    }
+    for (int64_t j = n4 * 4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += stride) {
+        float pp = p[j], mm = m[j], vv = v[j], ee = ema[j];
+        adam_elem(pp, pre_scale<CLIP>(g[j], gs), mm, vv, a);
+        ee = fmaf(omd_t, pp - ee, ee);
+        p[j] = pp; m[j] = mm; v[j] = vv; ema[j] = ee;
+    }
+}
+
 }  // namespace
+
+extern "C" int rt1_flat_adam_ema_dev(float* p, const float* g, float* m, float* v, float* ema, int64_t n,
+                                     const float* state, const float* clip_state, float* ema_state, float beta1,
+                                     float beta2, float eps, float weight_decay, float grad_scale,
+                                     float one_minus_decay, int warmup, hipStream_t stream) {
+    if (state == nullptr || ema == nullptr || ema_state == nullptr) return (int)hipErrorInvalidValue;
+    AdamArgs a{0.f, beta1, beta2, eps, weight_decay, 0.f, 1.f, grad_scale};
+    const int64_t n4 = n / 4;
+    int64_t blocks = (n4 + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    if (blocks < 1) blocks = 1;
+    if (clip_state != nullptr)
+        hipLaunchKernelGGL(flat_adam_ema_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, stream, p, g, m, v, ema,
+                           n4, n, a, state, clip_state, ema_state, one_minus_decay, warmup);
+    else
+        hipLaunchKernelGGL(flat_adam_ema_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, stream, p, g, m, v, ema,
+                           n4, n, a, state, clip_state, ema_state, one_minus_decay, warmup);
+    return (int)hipGetLastError();
+}
 
 extern "C" int rt1_flat_adam_clip_dev(float* p, const float* g, float* m, float* v, int64_t n, const float* state,
                                       const float* clip_state, float beta1, float beta2, float eps,

@@ -18,6 +18,13 @@ int rt1_flat_adam_dev(float* p, const float* g, float* m, float* v, int64_t n, c
 int rt1_flat_adam_clip_dev(float* p, const float* g, float* m, float* v, int64_t n, const float* state,
                            const float* clip_state, float beta1, float beta2, float eps, float weight_decay,
                            float grad_scale, hipStream_t stream);
+// rt1_flat_adam_dev (clip_state == nullptr) or rt1_flat_adam_clip_dev (otherwise) that also carries an exponential
+// moving average of the weights: ema += omd_t * (p_new - ema), omd_t = warmup ? max(one_minus_decay, 9 / (10 + t))
+// : one_minus_decay with t the Adam step of this call; ema_state fp32[4] <- {omd_t, t, 0, 0} of an applied update
+int rt1_flat_adam_ema_dev(float* p, const float* g, float* m, float* v, float* ema, int64_t n, const float* state,
+                          const float* clip_state, float* ema_state, float beta1, float beta2, float eps,
+                          float weight_decay, float grad_scale, float one_minus_decay, int warmup,
+                          hipStream_t stream);
 
 // gradnorm.hip (deterministic global gradient norm -> clip_state fp32[8] = {norm, coef, ok, skipped steps, clipped
 // steps, consecutive skipped steps, 0, 0}; rt1_gradnorm_partials: workgroups / fp64 partials for n floats, a function

@@ -28,7 +28,10 @@ class FlatAdam(torch.optim.Optimizer):
     def __init__(self, flat: FlatParameters, lr: float = 5e-4, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.0, all_params: Optional[Sequence[torch.nn.Parameter]] = None,
                  use_kernel: Optional[bool] = None, max_grad_norm: Optional[float] = None,
-                 skip_nonfinite: bool = False):
+                 skip_nonfinite: bool = False, ema_decay: float = 0.0, ema_warmup: bool = True,
+                 param_names: Optional[Dict[int, str]] = None):
+        if not 0.0 <= float(ema_decay) < 1.0:
+            raise ValueError(f"ema_decay must be in [0, 1) (0 = off), got {ema_decay!r}")
         self.flat = flat
         params = list(all_params) if all_params is not None else list(flat.params)
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False,
@@ -59,6 +62,21 @@ class FlatAdam(torch.optim.Optimizer):
             if self._kernel is not None:
                 self._partials = torch.zeros(self._kernel.gradnorm_partials(flat.grad.numel()), dtype=torch.float64,
                                              device=flat.data.device)
+        # exponential moving average of the trainable weights (off at 0): one more flat fp32 buffer, updated by the
+        # same launch as Adam (ops.adam.flat_adam_ema_dev_step).  ema_state is fp32[4] = {omd_t of the last applied
+        # update, its Adam step t, 0, 0} with omd = 1 - decay; under warm-up omd_t = max(omd, 9 / (10 + t)), i.e. the
+        # decay min(decay, (1 + t) / (10 + t)).  BN running statistics and frozen parameters are not in the flat buffer
+        # and are not averaged (torch.optim.swa_utils.AveragedModel's default).  The buffer is fp32: at decay 0.9999
+        # an update with |p - ema| below about 1e-3 |ema| moves it by less than an ulp (as in timm and torch).
+        self.ema_decay = float(ema_decay)
+        self.ema_warmup = bool(ema_warmup)
+        self.ema_enabled = self.ema_decay > 0.0
+        self.ema = self.ema_state = None
+        self._omd = 1.0 - self.ema_decay                # formed in double, rounded to fp32 once
+        self.param_names = param_names                  # {id(parameter): name} for ema_state_dict()
+        if self.ema_enabled:
+            self.ema = flat.data.detach().clone()
+            self.ema_state = torch.zeros(4, dtype=torch.float32, device=flat.data.device)
 
     @torch.no_grad()
     def step(self, closure=None, grad_scale: float = 1.0):
@@ -80,6 +98,14 @@ class FlatAdam(torch.optim.Optimizer):
                 self._kernel.grad_norm_clip_(self.flat.grad, self.clip_state, self._partials,
                                              max_norm=self.max_grad_norm, grad_scale=grad_scale,
                                              skip_nonfinite=self.skip_nonfinite)
+            if self.ema_enabled:
+                self._kernel.flat_adam_ema_dev_step(self.flat.data, self.flat.grad, self.exp_avg, self.exp_avg_sq,
+                                                    self.ema, self.dev_state, self.ema_state, self.clip_state,
+                                                    beta1=b1, beta2=b2, eps=eps, weight_decay=wd,
+                                                    grad_scale=grad_scale, one_minus_decay=self._omd,
+                                                    warmup=self.ema_warmup)
+                return loss
+            if self.clip_enabled:
                 self._kernel.flat_adam_clip_dev_step(self.flat.data, self.flat.grad, self.exp_avg, self.exp_avg_sq,
                                                      self.dev_state, self.clip_state, beta1=b1, beta2=b2, eps=eps,
                                                      weight_decay=wd, grad_scale=grad_scale)
@@ -108,6 +134,11 @@ class FlatAdam(torch.optim.Optimizer):
         bc2 = 1.0 - b2 ** t
         denom = (self.exp_avg_sq.sqrt() / math.sqrt(bc2)).add_(eps)
         p.addcdiv_(self.exp_avg, denom, value=-lr / bc1)
+        if self.ema_enabled:
+            # the kernel's recurrence in torch: omd_t in fp32 from the same t, ema += omd_t * (p - ema)
+            omd_t = self._omd_t(t)
+            self.ema_state.copy_(torch.stack([omd_t, torch.tensor(float(t)), torch.zeros(()), torch.zeros(())]))
+            self.ema.add_((p - self.ema).mul_(omd_t.to(p.device)))
         return loss
 
     def _clip_verdict(self, grad: torch.Tensor):
@@ -136,6 +167,64 @@ class FlatAdam(torch.optim.Optimizer):
     @property
     def clipped_steps(self) -> int:
         return int(self.clip_state[4]) if self.clip_state is not None else 0
+
+    # -------------------------------------------------------------- exponential moving average of the weights
+    @property
+    def ema_decay_now(self) -> Optional[torch.Tensor]:
+        """The decay the last applied update used (``1 - ema_state[0]``): a 0-d device tensor, no sync."""
+        return 1.0 - self.ema_state[0] if self.ema_state is not None else None
+
+    @property
+    def ema_num_updates(self) -> int:
+        """Adam step of the last applied EMA update (skipped steps do not count)."""
+        return int(self.ema_state[1]) if self.ema_state is not None else 0
+
+    @torch.no_grad()
+    def reset_ema(self):
+        """``ema <- data`` (the weights were replaced from outside and there is no average to restore)."""
+        if self.ema is not None:
+            self.ema.copy_(self.flat.data)
+
+    def ema_state_dict(self) -> Dict[str, torch.Tensor]:
+        """The average per trainable parameter, keyed by name, over the parameters and offsets ``state_dict()`` walks."""
+        if self.ema is None:
+            raise RuntimeError("the EMA is off (ema_decay = 0)")
+        return {name: self.ema[o:o + p.numel()].view_as(p).detach().clone()
+                for name, p, o in zip(self._param_names(), self.flat.params, self.flat.offsets)}
+
+    @torch.no_grad()
+    def load_ema_state_dict(self, sd: Dict[str, torch.Tensor], num_updates: Optional[int] = None):
+        if self.ema is None:
+            raise RuntimeError("the EMA is off (ema_decay = 0)")
+        names = self._param_names()
+        missing = [n for n in names if n not in sd]
+        if missing:
+            raise KeyError(f"EMA state lacks {len(missing)} parameters, e.g. {missing[0]!r}")
+        for name, p, o in zip(names, self.flat.params, self.flat.offsets):
+            self.ema[o:o + p.numel()].copy_(sd[name].reshape(-1))
+        if num_updates is not None:
+            # {omd_t, t} as the update that produced this average left them (the next update rewrites both)
+            t = int(num_updates)
+            omd_t = self._omd_t(t) if t > 0 else torch.zeros(())
+            self.ema_state.copy_(torch.stack([omd_t, torch.tensor(float(t)), torch.zeros(()), torch.zeros(())]))
+
+    def _omd_t(self, t: int) -> torch.Tensor:
+        """One minus the decay of Adam step ``t`` as the kernel forms it, in fp32 (a 0-d host tensor)."""
+        omd = torch.tensor(self._omd, dtype=torch.float32)
+        if not self.ema_warmup:
+            return omd
+        f32 = lambda x: torch.tensor(float(x), dtype=torch.float32)
+        return torch.maximum(omd, f32(9) / (f32(10) + f32(t)))
+
+    def _param_names(self) -> List[str]:
+        """Names of ``flat.params`` in flat order: the model's (``param_names``), else the ``state_dict()`` index."""
+        if self.param_names is not None:
+            return [self.param_names[id(p)] for p in self.flat.params]
+        pos: Dict[int, int] = {}
+        for g in self.param_groups:
+            for p in g["params"]:
+                pos.setdefault(id(p), len(pos))
+        return [str(pos[id(p)]) for p in self.flat.params]
 
     def write_device_state(self, step: int, lr: float):
         """Host -> device write of {step, lr} (a small H2D copy; outside any capture)."""

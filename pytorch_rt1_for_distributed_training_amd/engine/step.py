@@ -37,6 +37,14 @@ window starts with the one memset of the flat gradient.  With ``graph=True`` the
 data parallelism only the final micro-batch all-reduces.  BN running statistics advance once per micro-batch; their
 shadow is the state before the window, so a skipped window rolls all of it back.
 
+``ema_decay=d`` (0 = off, and then nothing here changes): the optimizer keeps an exponential moving average of the
+trainable weights in one more flat fp32 buffer, updated by the Adam launch itself (``ops.adam.flat_adam_ema_dev_step``:
+``ema += omd_t * (p - ema)``, the warm-up schedule formed on the device from the same step the bias corrections use), so
+every step path above carries it and a skipped step leaves it untouched.  BN running statistics and the frozen
+``_action_token_emb`` are not averaged: ``ema_weights()`` runs the averaged weights with the live BN buffers
+(``torch.optim.swa_utils.AveragedModel``'s default).  The buffer is fp32: at decay 0.9999 an update whose ``|p - ema|`` is
+below about ``1e-3 |ema|`` moves it by less than an ulp.
+
 No ``network_state`` is fabricated (the reference samples a random one on the
 CPU and copies it to the GPU every step only to read its shape).
 """
@@ -123,7 +131,7 @@ class TrainEngine:
                  broadcast_buffers: bool = True, device: Optional[torch.device] = None,
                  grad_comm_dtype: torch.dtype = torch.float32, order_probe: bool = True, comm: str = "torch",
                  graph: bool = False, max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False,
-                 accumulate_grad_batches: int = 1):
+                 accumulate_grad_batches: int = 1, ema_decay: float = 0.0, ema_warmup: bool = True):
         if int(accumulate_grad_batches) != accumulate_grad_batches or accumulate_grad_batches < 1:
             raise ValueError(f"accumulate_grad_batches must be an integer >= 1, got {accumulate_grad_batches!r}")
         ctx = pdist.context()
@@ -164,7 +172,8 @@ class TrainEngine:
                                 broadcast_buffers=broadcast_buffers, grad_comm_dtype=grad_comm_dtype, comm=native)
         self.optimizer = FlatAdam(self.flat, lr=lr, weight_decay=weight_decay,
                                   all_params=list(self.model.parameters()), max_grad_norm=max_grad_norm,
-                                  skip_nonfinite=skip_nonfinite)
+                                  skip_nonfinite=skip_nonfinite, ema_decay=ema_decay, ema_warmup=ema_warmup,
+                                  param_names={id(p): n for n, p in self.model.named_parameters()})
         # skip_nonfinite: the forward of a bad batch has already written the BN running statistics when the norm
         # kernel notices, so they live in one flat buffer (the data-parallel one when there is one) with a shadow copy
         # of the last good state; buffer_guard_ advances or rolls back right after the optimizer step
@@ -565,7 +574,9 @@ class TrainEngine:
                         shadow=(self._bn_shadow.clone() if self._bn_shadow is not None else None),
                         # an open accumulation window is state too: what it gathered so far and its position
                         grad=(self.flat.grad.clone() if self.accumulate_grad_batches > 1 else None),
-                        micro=self.micro_step, stepped=self.stepped)
+                        micro=self.micro_step, stepped=self.stepped,
+                        ema=(opt.ema.clone() if opt.ema is not None else None),
+                        ema_state=(opt.ema_state.clone() if opt.ema_state is not None else None))
 
     def _restore(self, s: Dict):
         from ..ops import rng as _rng
@@ -585,6 +596,9 @@ class TrainEngine:
                 self._bn_shadow.copy_(s["shadow"])
             if s["grad"] is not None:
                 self.flat.grad.copy_(s["grad"])
+            if s["ema"] is not None:
+                opt.ema.copy_(s["ema"])
+                opt.ema_state.copy_(s["ema_state"])
         self.micro_step, self.stepped = s["micro"], s["stepped"]
         opt.step_count, opt._dev_step, opt._dev_lr = s["step"], s["dev_step"], s["dev_lr"]
         if s["rng"] is not None:
@@ -612,6 +626,8 @@ class TrainEngine:
             if self.device.type == "cuda":
                 torch.cuda.synchronize(self.device)
             grad_g, data_g = self.flat.grad.clone(), self.flat.data.clone()
+            opt = self.optimizer
+            ema_g = (opt.ema.clone(), opt.ema_state.clone()) if opt.ema is not None else None
             self._restore(snap)
             loss_e = (self._eager_micro_step(batch) if self.accumulate_grad_batches > 1 else self._step_body(batch))
             if self.device.type == "cuda":
@@ -619,6 +635,8 @@ class TrainEngine:
             res = dict(grads=bool(torch.equal(grad_g, self.flat.grad)),
                        params=bool(torch.equal(data_g, self.flat.data)),
                        loss=bool(torch.equal(loss_g, loss_e)))
+            if ema_g is not None:
+                res["ema"] = bool(torch.equal(ema_g[0], opt.ema) and torch.equal(ema_g[1], opt.ema_state))
             if not res["grads"]:
                 res["max_grad_diff"] = float((grad_g - self.flat.grad).abs().max())
         finally:
@@ -626,8 +644,32 @@ class TrainEngine:
             self.comm_timing = timing
             if self.device.type == "cuda":
                 torch.cuda.synchronize(self.device)
-        res["equal"] = res["grads"] and res["params"] and res["loss"]
+        res["equal"] = res["grads"] and res["params"] and res["loss"] and res.get("ema", True)
         return res
+
+    # ------------------------------------------------------------------ averaged weights
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Run the model on the exponential moving average of its weights: inside the context ``flat.data`` holds
+        ``optimizer.ema``, on exit the live weights are copied back.  Content copies only, so every address -- and
+        with it a captured graph and the bf16 weight shadow, which is refreshed from the flat buffer on each
+        forward -- stays valid.  Only the trainable parameters are averaged: BN running statistics and the frozen
+        ``_action_token_emb`` are the live ones (``torch.optim.swa_utils.AveragedModel``'s default).  For evaluation;
+        a ``train_step`` inside the context would train the average."""
+        opt = self.optimizer
+        if opt.ema is None:
+            raise RuntimeError("ema_weights(): the EMA is off (ema_decay = 0)")
+        if self.micro_step != 0:
+            raise RuntimeError(f"ema_weights(): an accumulation window is open ({self.micro_step} micro-batches); "
+                               f"finish or flush it first")
+        with torch.no_grad():
+            saved = self.flat.data.clone()
+            self.flat.data.copy_(opt.ema)
+        try:
+            yield self
+        finally:
+            with torch.no_grad():
+                self.flat.data.copy_(saved)
 
     @torch.no_grad()
     def eval_step(self, batch: Dict) -> torch.Tensor:

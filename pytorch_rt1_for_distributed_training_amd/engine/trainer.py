@@ -24,6 +24,10 @@ With the engine's ``accumulate_grad_batches=k`` a ``train_step`` is one micro-ba
 ``global_step`` count optimizer steps (as Lightning does), ``train_loss_step`` is the mean over the micro-batches of
 the logged windows, and a window left open when an epoch's batches run out is applied (``engine.flush_window``) before
 validation, the LR scheduler and checkpointing, so no checkpoint ever holds a half-accumulated gradient.
+
+With the engine's ``ema_decay > 0`` every validation also runs on the averaged weights and logs ``eval_loss_ema``,
+checkpoints carry the average under one more top-level key, ``"ema"``, and ``resume`` restores it (or starts it at the
+restored weights when the checkpoint has none).  ``eval_loss`` and the checkpoint file names are those of the live weights.
 """
 from __future__ import annotations
 
@@ -36,7 +40,8 @@ import torch
 
 from ..data.prefetch import DevicePrefetcher
 from ..parallel import dist as pdist
-from ..utils.checkpoint import ModelCheckpoint, build_checkpoint, load_checkpoint, load_model_state
+from ..utils.checkpoint import (PREFIX, ModelCheckpoint, build_checkpoint, ema_entry, load_checkpoint,
+                                load_model_state)
 from ..utils.logging import MultiLogger
 from .step import TrainEngine
 
@@ -67,6 +72,9 @@ class Trainer:
         self.verbose = verbose and pdist.context().is_main
         self.current_epoch = 0
         self.history: Dict[str, list] = {"train_loss_epoch": [], "eval_loss": [], "samples_per_sec": []}
+        self.last_ema_loss = None                # validate(): loss on the averaged weights (engine EMA on)
+        if getattr(engine.optimizer, "ema", None) is not None:
+            self.history["eval_loss_ema"] = []
         self.graph_checked = False
         self.graph_check = None
 
@@ -96,7 +104,7 @@ class Trainer:
     def _make_ckpt(self, callbacks):
         e = self.engine
         return build_checkpoint(e.model, e.optimizer, e.scheduler, epoch=self.current_epoch,
-                                global_step=e.global_step, callbacks=callbacks)
+                                global_step=e.global_step, callbacks=callbacks, ema=ema_entry(e.optimizer))
 
     def _check_graph(self, batch):
         """Once, right after the hipGraph step is captured: one replayed step and one eager step on the same batch from
@@ -131,8 +139,19 @@ class Trainer:
         if self.engine.ddp.enabled:
             self.engine.ddp.broadcast_parameters()
         self.engine.refresh_buffer_shadow()
+        opt = self.engine.optimizer
+        if getattr(opt, "ema", None) is not None:
+            # every rank reads the same file, so the restored average needs no broadcast; a checkpoint without one
+            # (trained with the EMA off) starts the average at the restored weights
+            ema = ck.get("ema")
+            if isinstance(ema, dict) and ema.get("state_dict"):
+                opt.load_ema_state_dict({k[len(PREFIX):] if k.startswith(PREFIX) else k: v
+                                         for k, v in ema["state_dict"].items()},
+                                        num_updates=int(ema.get("num_updates", 0)))
+            else:
+                opt.reset_ema()
 
-    def validate(self, loader, limit=None, name="eval_loss") -> float:
+    def _eval_mean(self, loader, limit) -> float:
         total, n = None, 0
         for batch in self._iter(loader, limit):
             loss = self.engine.eval_step(batch)
@@ -141,6 +160,18 @@ class Trainer:
         if total is None:
             total = torch.zeros((), device=self.engine.device)
         return self._mean_across(total, n)
+
+    def validate(self, loader, limit=None, name="eval_loss") -> float:
+        """Mean loss over ``loader`` with the live weights (the return value).  With the engine's EMA on the pass
+        runs once more on the averaged weights (``TrainEngine.ema_weights``) and logs ``<name>_ema``; the value is
+        kept in ``last_ema_loss``."""
+        loss = self._eval_mean(loader, limit)
+        self.last_ema_loss = None
+        if getattr(self.engine.optimizer, "ema", None) is not None:
+            with self.engine.ema_weights():
+                self.last_ema_loss = self._eval_mean(loader, limit)
+            self._log({name + "_ema": self.last_ema_loss})
+        return loss
 
     def fit(self, train_loader: Iterable, val_loader: Optional[Iterable] = None):
         """Train on a high-priority HIP stream when batches are decoded on the device: the prefetch stream's decode
@@ -248,6 +279,8 @@ class Trainer:
             if val_loader is not None:
                 metrics["eval_loss"] = self.validate(val_loader, self.limit_val)
             self._log(metrics)
+            if val_loader is not None and self.last_ema_loss is not None:
+                metrics["eval_loss_ema"] = self.last_ema_loss        # validate() logged it already
             for k in self.history:
                 if k in metrics:
                     self.history[k].append(metrics[k])

@@ -38,10 +38,11 @@ class RT1Policy:
 
     @classmethod
     def from_checkpoint(cls, path: str, cfg: Optional[RT1Config] = None, device=None, backend: str = "auto",
-                        **kw) -> "RT1Policy":
+                        use_ema: bool = False, **kw) -> "RT1Policy":
+        """``use_ema``: act from the checkpoint's averaged weights (its ``"ema"`` entry; an error when it has none)."""
         cfg = cfg or RT1Config()
         model = build_rt1(cfg)
-        load_model_state(model, load_checkpoint(path))
+        load_model_state(model, load_checkpoint(path), use_ema=use_ema)
         return cls(model, device=device, cfg=cfg, backend=backend, **kw)
 
     @property

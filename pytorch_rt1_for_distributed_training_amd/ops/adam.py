@@ -49,6 +49,28 @@ def flat_adam_clip_dev_step(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v
     load().flat_adam_clip_dev(p, g, m, v, state, clip_state, beta1, beta2, eps, weight_decay, grad_scale)
 
 
+EMA_STATE_SLOTS = 4    # {omd_t used by the last applied update, t of that update, 0, 0}
+
+
+def flat_adam_ema_dev_step(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, ema: torch.Tensor,
+                           state: torch.Tensor, ema_state: torch.Tensor, clip_state: torch.Tensor = None, *,
+                           beta1: float, beta2: float, eps: float, weight_decay: float, grad_scale: float = 1.0,
+                           one_minus_decay: float, warmup: bool = True):
+    """``flat_adam_dev_step`` (``clip_state=None``) or ``flat_adam_clip_dev_step`` -- ``p, m, v`` come out bit for bit
+    the same -- that also carries the exponential moving average of the weights in the same launch:
+    ``ema += omd_t * (p_new - ema)`` with ``omd_t = max(one_minus_decay, 9 / (10 + t))`` under warm-up (the decay
+    ``min(decay, (1 + t) / (10 + t))``) and ``one_minus_decay`` without, ``t`` being the Adam step of this call as
+    the device sees it.  ``ema_state`` fp32[4] receives ``{omd_t, t, 0, 0}``; a skipped step touches neither."""
+    load().flat_adam_ema_dev(p, g, m, v, ema, state, ema_state, clip_state, beta1, beta2, eps, weight_decay,
+                             grad_scale, float(one_minus_decay), bool(warmup))
+
+
+def reference_ema_step(ema: torch.Tensor, p: torch.Tensor, omd_t) -> torch.Tensor:
+    """fp64 oracle of one EMA update, ``ema + omd_t * (p - ema)``; returns fp64 and modifies nothing."""
+    e = ema.double()
+    return e + float(omd_t) * (p.double() - e)
+
+
 def buffer_guard_(buf: torch.Tensor, shadow: torch.Tensor, clip_state: torch.Tensor):
     """ok ? ``shadow = buf`` : ``buf = shadow`` (one launch): rolls back what a skipped step's forward wrote."""
     load().buffer_guard_(buf, shadow, clip_state)

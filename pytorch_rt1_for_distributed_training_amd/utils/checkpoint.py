@@ -30,7 +30,11 @@ def lightning_state_dict(model: torch.nn.Module) -> Dict[str, torch.Tensor]:
 
 
 def build_checkpoint(model, optimizer=None, scheduler=None, epoch: int = 0, global_step: int = 0,
-                     callbacks: Optional[Dict[str, Any]] = None, extra: Optional[Dict[str, Any]] = None) -> Dict:
+                     callbacks: Optional[Dict[str, Any]] = None, extra: Optional[Dict[str, Any]] = None,
+                     ema: Optional[Dict[str, Any]] = None) -> Dict:
+    """``ema`` (``ema_entry``; only with the optimizer's weight averaging on) adds ONE top-level key, ``"ema"``:
+    ``{"decay", "warmup", "num_updates", "state_dict": {"model.<name>": cpu tensor}}`` over the trainable parameters.
+    Without it the layout is exactly Lightning's."""
     ck: Dict[str, Any] = {
         "epoch": int(epoch),
         "global_step": int(global_step),
@@ -43,7 +47,18 @@ def build_checkpoint(model, optimizer=None, scheduler=None, epoch: int = 0, glob
     }
     if extra:
         ck.update(extra)
+    if ema is not None:
+        ck["ema"] = ema
     return ck
+
+
+def ema_entry(optimizer) -> Optional[Dict[str, Any]]:
+    """The ``"ema"`` checkpoint entry of a ``FlatAdam`` with weight averaging on; None when it is off."""
+    if getattr(optimizer, "ema", None) is None:
+        return None
+    return {"decay": float(optimizer.ema_decay), "warmup": bool(optimizer.ema_warmup),
+            "num_updates": int(optimizer.ema_num_updates),
+            "state_dict": {PREFIX + k: v.cpu() for k, v in optimizer.ema_state_dict().items()}}
 
 
 def _cpu(obj):
@@ -67,10 +82,24 @@ def load_checkpoint(path: str, map_location="cpu") -> Dict:
     return torch.load(path, map_location=map_location, weights_only=True)
 
 
-def load_model_state(model: torch.nn.Module, ckpt_or_path, strict: bool = True):
+def _strip(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    return {k[len(PREFIX):] if k.startswith(PREFIX) else k: v for k, v in sd.items()}
+
+
+def load_model_state(model: torch.nn.Module, ckpt_or_path, strict: bool = True, use_ema: bool = False):
+    """Load ``state_dict``; with ``use_ema`` the averaged weights of the ``"ema"`` entry are then laid over the
+    trainable parameters (BN running statistics and frozen parameters stay the live ones)."""
     ck = load_checkpoint(ckpt_or_path) if isinstance(ckpt_or_path, str) else ckpt_or_path
-    sd = ck.get("state_dict", ck)
-    sd = {k[len(PREFIX):] if k.startswith(PREFIX) else k: v for k, v in sd.items()}
+    sd = _strip(ck.get("state_dict", ck))
+    if use_ema:
+        ema = ck.get("ema")
+        if not isinstance(ema, dict) or not ema.get("state_dict"):
+            raise KeyError("use_ema=True, but the checkpoint has no 'ema' entry (it was trained with --ema_decay 0)")
+        avg = _strip(ema["state_dict"])
+        unknown = [k for k in avg if k not in sd]
+        if unknown:
+            raise KeyError(f"the checkpoint's EMA holds {len(unknown)} names its state_dict lacks, e.g. {unknown[0]!r}")
+        sd = dict(sd, **avg)
     with torch.no_grad():
         return model.load_state_dict(sd, strict=strict)
 
