@@ -70,6 +70,12 @@ def build(verbose: bool = False, jobs: int = 8, clean: bool = False, defines=(),
     kernels = sorted(glob.glob(os.path.join(CSRC, "kernels", "*.hip")))
     common = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-I", CSRC,
               "-Wno-unused-result", "-Wno-unused-command-line-argument"] + dflags
+    host_srcs = sorted(glob.glob(os.path.join(CSRC, "*.cpp")))     # bindings.cpp, comm.cpp: torch-facing host code
+    # an object whose source no longer exists is not linked, but tools that read the object directory would still see it
+    live = {os.path.basename(s) + ".o" for s in kernels + host_srcs}
+    for obj in glob.glob(os.path.join(BUILD_DIR, "*.o")):
+        if os.path.basename(obj) not in live:
+            os.remove(obj)
     jobs_list = []
     objs = []
     for src in kernels:
@@ -79,7 +85,6 @@ def build(verbose: bool = False, jobs: int = 8, clean: bool = False, defines=(),
             jobs_list.append([HIPCC] + common + ["-munsafe-fp-atomics", "-c", src, "-o", obj])
     inc, libs, abi = _torch_paths()
     py_inc = sysconfig.get_paths()["include"]
-    host_srcs = sorted(glob.glob(os.path.join(CSRC, "*.cpp")))     # bindings.cpp, comm.cpp: torch-facing host code
     for src in host_srcs:
         obj = os.path.join(BUILD_DIR, os.path.basename(src) + ".o")
         objs.append(obj)

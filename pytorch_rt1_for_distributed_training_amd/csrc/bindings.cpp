@@ -611,7 +611,7 @@ at::Tensor dw_bwd_weight(at::Tensor dy, at::Tensor x, OptT scale, OptT shift, in
     return sum0(part).view({C, k * k});
 }
 
-// Whole stride-1 depthwise backward in one pass (dwconv.hip dw_bwd_fused_kernel): dy = BN2-backward-apply(dA, y2)
+// Whole stride-1 depthwise backward in one pass (dw_bwd_s1.hip rt1_dw_bwd_fused): dy = BN2-backward-apply(dA, y2)
 // is rebuilt in the staging prologue (gate / rb [N, C]; BN2 scale, shift, mean, rstd, gamma, mdz, mdzx [C]) and
 // feeds both dx = dwconv^T(dy) and dW = sum dy (x) act(x1*scale1+shift1).  mean1/rstd1 select the BN1 epilogue
 // (expand blocks, x1 = y1): returns {dx, dW [C, k*k], pdz, pdzx}; otherwise {dx, dW}.

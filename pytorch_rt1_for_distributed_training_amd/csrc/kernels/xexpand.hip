@@ -5,7 +5,7 @@
 //     sum_m y1[m, c]    = w_c . sx            sx = sum_m x[m, :]            (Cin)
 //     sum_m y1[m, c]^2  = w_c^T G w_c         G  = x^T x                    (Cin x Cin)
 // so BN1 (film_efficientnet_encoder.py:185-195, train mode) never needs y1 itself: the depthwise kernels recompute
-// it per tile on MFMA (dwconv.hip stage_xmfma) and this kernel turns (G, sx) into BN1's constants with the same
+// it per tile on MFMA (dw/dw_stage.h stage_xmfma) and this kernel turns (G, sx) into BN1's constants with the same
 // finalisation as bn_finalize (bn.hip): biased variance for the normalisation, the unbiased one for the running
 // estimate, momentum update in place.  Everything after G is fp64: the quadratic form subtracts mean^2 from E[y^2].
 //

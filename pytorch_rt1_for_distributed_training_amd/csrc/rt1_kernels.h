@@ -62,7 +62,9 @@ int rt1_bn_bwd_apply(const rt1_bf16* G, const float* rs, const float* rb, int64_
                      const float* gamma, int act, const float* mdz, const float* mdzx, rt1_bf16* dy, hipStream_t st,
                      const float* keep = nullptr);   // keep [N]: rs[n] * keep[n] (the drop-path mask)
 
-// dwconv.hip
+// depthwise conv -- dw_plan.hip: the *_grid helpers, rt1_dw_grid_x, rt1_dw_bwd_uses_uni, rt1_dw_x_supported,
+// rt1_dw_tile_info (host only); dw_fwd.hip: rt1_dw_fwd, rt1_dw_fwd_x, rt1_dw_bwd_data, rt1_dw_bwd_weight;
+// dw_bwd_s1.hip: rt1_dw_bwd_fused; dw_bwd_s2.hip: rt1_dw_bwd_fused_s2
 int rt1_dw_grid(int N, int H, int W, int C, int k, int s, int max_blocks_x, int pro, int epi);
 int rt1_dw_wgrad_grid(int N, int H, int W, int C, int k, int s, int max_blocks_x, int pro);
 int rt1_dw_bwd_grid(int N, int H, int W, int C, int k, int s, int max_blocks_x, int epi);

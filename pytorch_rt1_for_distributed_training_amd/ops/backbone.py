@@ -5,7 +5,7 @@ Activations are channels-last bf16 ``[N, H, W, C]`` (N = b*t frames) end to end;
 and every reduction are fp32/fp64 with a fixed summation order.  Per MBConv block:
 
 forward   y1 = x @ We^T + BN1 constants  expand 1x1
-          y2 = dwconv(silu(bn1(y1)))    dw_fwd_kernel (dwconv.hip): BN1+SiLU prologue while staging the tile, BN2
+          y2 = dwconv(silu(bn1(y1)))    dw_fwd_kernel (dw_fwd.hip): BN1+SiLU prologue while staging the tile, BN2
                                          partials epilogue
           s  = SE(mean_hw silu(bn2(y2))) frame_pool + fp32 fc1 / SiLU / fc2 / sigmoid
           y3 = (silu(bn2(y2)) * s) @ Wp^T project 1x1 + BN3 constants
@@ -145,7 +145,7 @@ class RouteFlags:
     # GEMMs per step.  z_gemm=1 (default since the round-5 re-check, profiles/r5_switch_recheck_ab.log: +0.15 %): blocks
     # 19-24 only; 2: also block 25's 2304 -> 384; 0: the bn_bwd_apply + library path.
     z_gemm: str
-    # y1-free expand blocks ("x-mode", csrc/kernels/dwconv.hip stage_xmfma + xexpand.hip): the expand output y1 is never
+    # y1-free expand blocks ("x-mode", csrc/kernels/dw/dw_stage.h stage_xmfma + xexpand.hip): the expand output y1 is never
     # written.  BN1's batch statistics come from the block input's Gram matrix (sum y1 = We sum x, sum y1^2 = w^T G w),
     # the depthwise forward and its unified backward recompute y1 = x @ We^T per staged tile on MFMA, and the expand
     # backward is the dz-mode pw_bwd_z (it reads dz and x only).  Removes the expand GEMM's write of y1 and both depthwise
@@ -877,7 +877,7 @@ class MBConvFn(torch.autograd.Function):
             d1, dWd, bn1p = res[0], res[1].view_as(Wd), res[2:4]
         elif r.dw_bwd == "fused":
             # BN2 backward-apply + depthwise data AND weight gradients in one pass; dy2 never reaches HBM
-            # (csrc/kernels/dwconv.hip dw_bwd_uni_kernel / dw_bwd_uni_s2_kernel)
+            # (csrc/kernels/dw_bwd_s1.hip dw_bwd_uni_kernel / dw_bwd_s2.hip dw_bwd_uni_s2_kernel)
             # non-expand residual block (block 1): the residual gradient dout * fmul joins dx in the kernel's store
             res = ext.dw_bwd_fused(dA.view(N, H2, W2, Ce), y2, gate, rb.contiguous(), sc2, sh2, mu2, rs2,
                                    g2.float().contiguous(), mdz2, mdzx2, wd, k, x1, sc1, sh1,

@@ -1,11 +1,13 @@
-"""fp64 references and the element-wise oracle for the depthwise kernels (csrc/kernels/dwconv.hip).
+"""fp64 references and the element-wise oracle for the depthwise kernels (csrc/kernels/dw_*.hip).
 
 Plain torch, CPU or GPU tensors, no extension call.  Activations are NHWC bf16 [N, H, W, C], weights [C, k*k] fp32 with
 tap t = kh*k + kw, pad (k-1)/2.  Every reference is a sum over the k*k taps of shifted slices of a zero-padded NHWC
 tensor and returns (ref, S) with S the same tap sum over absolute values, S = sum_t |w_t| * S_operand_t (glue_oracle's
 convention: the magnitude that the fp32 roundings are relative to).
 
-What the kernels compute, read from dwconv.hip and cited by function:
+What the kernels compute, read from the kernel units and cited by function (dw_fwd.hip: stage_tile_t, epilogue<EPI>,
+dw_fwd_kernel, the dw_bwd_data kernel, dw_bwd_weight_kernel, dw_bwd_fused_kernel; dw_bwd_s1.hip: stage_dy_half,
+dw_bwd_uni_kernel; dw_bwd_s2.hip: uni_s2_class; dw/dw_stage.h: zero_ring, stage_dy; dw/dw_uni.h: centre_silu):
   * Zero padding applies to the operand AFTER its prologue: stage_tile_t and stage_dy / stage_dy_half write zeros for
     the ring and for out-of-image pixels (zero_ring; `if (!ok[k]) v = 0`), the prologue runs only on loaded pixels
     (stage_tile_t: `if (PRO != PRO_COPY && (valid >> k & 1u))`).

@@ -1,4 +1,4 @@
-"""The depthwise kernels of csrc/kernels/dwconv.hip against the fp64 oracle of tests/dw_oracle.py on every kernel route
+"""The depthwise kernels of csrc/kernels/dw_*.hip against the fp64 oracle of tests/dw_oracle.py on every kernel route
 (MI355X only): element-wise bounds on every bf16 output, derived bounds on the weight gradient and on the column sums of
 the partial rows, and a bitwise repeat (every reduction here has a fixed order).
 

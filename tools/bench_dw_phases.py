@@ -5,7 +5,8 @@ build of the extension (build.py --variant <name> -D RT1_DW_TIMING=<mask>, loade
 
   python tools/bench_dw_phases.py [--frames 768] [--res 300] [--blocks 6,14,19] [--tag base]
 
-Timing builds (csrc/kernels/dwconv.hip, RT1_DW_TIMING bit mask):
+Timing builds (csrc/kernels/dw_fwd.hip, dw_bwd_s1.hip and the staging headers under dw/; RT1_DW_TIMING bit mask,
+default in dw/dw_common.h):
   2   no LDS staging of the input / dy tile (the tile holds stale data)
   4   no K x K tap loop (data and weight products)
   16  backward: no strip-centre x1 loads / BN1 + SiLU recompute

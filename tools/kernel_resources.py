@@ -2,7 +2,7 @@
 """VGPR / SGPR / scratch / LDS per kernel of a built object (build/hip/<unit>.o), from the code object's metadata
 notes -- the register budget check for a kernel edit, no GPU needed.
 
-    python tools/kernel_resources.py build/hip/dwconv.hip.o [name-filter]
+    python tools/kernel_resources.py build/hip/dw_bwd_s1.hip.o [name-filter]
 """
 import os
 import re

@@ -5,12 +5,14 @@ usage: python tools/prof_diff.py gpurun_out/prof_X0 gpurun_out/prof_X1 [--steps 
 """
 import argparse
 import csv
+import re
 
 
 def load(d, steps):
     out = {}
     for r in csv.DictReader(open(f"{d}/run_kernel_stats.csv")):
-        k = r["Name"][:100]
+        # namespace qualifiers dropped: a kernel whose parameter structs moved to another namespace pairs with itself
+        k = re.sub(r"(\(anonymous namespace\)|\b[A-Za-z_]\w*)::", "", r["Name"])[:100]
         c, t = out.get(k, (0, 0.0))
         out[k] = (c + int(r["Calls"]), t + float(r["TotalDurationNs"]) / 1e6 / steps)
     return out
