@@ -56,6 +56,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--backend", choices=["auto", "hip", "torch"], default="auto")
     p.add_argument("--num_layers", type=int, default=8)
     p.add_argument("--weight_decay", type=float, default=0.0, help="AdamW decoupled decay (0 = Adam, reference)")
+    p.add_argument("--no_decay_norm_bias", action="store_true",
+                   help="--weight_decay skips BatchNorm / LayerNorm scales and shifts, every bias and the embeddings "
+                        "(their own parameter group inside the one fused Adam launch)")
+    p.add_argument("--backbone_lr_mult", type=float, default=1.0,
+                   help="learning rate of the pretrained EfficientNet-B3 backbone as a multiple of --lr (> 0; needs "
+                        "--pretrained or --resume: without pretrained weights there is nothing to protect)")
     p.add_argument("--gradient_clip_val", type=float, default=0.0,
                    help="clip the global gradient norm to this value on the device (Lightning's name; 0 = off)")
     p.add_argument("--skip_nonfinite_steps", action="store_true",
@@ -218,11 +224,16 @@ def train(args):
                          max_grad_norm=args.gradient_clip_val if args.gradient_clip_val > 0 else None,
                          skip_nonfinite=args.skip_nonfinite_steps,
                          accumulate_grad_batches=args.accumulate_grad_batches, ema_decay=args.ema_decay,
-                         ema_warmup=not args.no_ema_warmup)
+                         ema_warmup=not args.no_ema_warmup, no_decay_norm_bias=args.no_decay_norm_bias,
+                         backbone_lr_mult=args.backbone_lr_mult, pretrained=bool(args.pretrained or args.resume))
     if ctx.is_main:
         print(f"[train] gradient_clip_val {args.gradient_clip_val if args.gradient_clip_val > 0 else 'off'}, "
               f"skip_nonfinite_steps {'on' if args.skip_nonfinite_steps else 'off'}, "
               f"accumulate_grad_batches {args.accumulate_grad_batches}", flush=True)
+        if len(engine.lrs) > 1:
+            print("[train] parameter groups: " + ", ".join(
+                f"{g.get('name')} ({len(g['params'])} tensors, lr {g['lr']:.3g}, weight_decay {g['weight_decay']:g})"
+                for g in engine.optimizer.param_groups), flush=True)
         if args.ema_decay > 0:
             print(f"[train] ema_decay {args.ema_decay} (warm-up {'off' if args.no_ema_warmup else 'on'})", flush=True)
     ckpt = ModelCheckpoint(os.path.join(args.ckpt_dir, args.exp_name), every_n_epochs=args.ckpt_every_n_epochs)
@@ -282,8 +293,19 @@ def debug(args):
     print(f"seq_idx:{state['seq_idx'].tolist()}")
 
 
+def check_args(parser, args):
+    """Refusals that need no model: a flag combination that cannot mean what it says."""
+    if not args.backbone_lr_mult > 0:
+        parser.error(f"--backbone_lr_mult must be > 0, got {args.backbone_lr_mult}")
+    if args.backbone_lr_mult != 1.0 and not (args.pretrained or args.resume):
+        parser.error("--backbone_lr_mult needs --pretrained or --resume: a randomly initialised backbone has no "
+                     "pretrained weights to protect with a smaller learning rate")
+
+
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    check_args(parser, args)
     gpus = [g for g in args.gpus.split(",") if g.strip() != ""]
     if args.mode == "train" and args.device != "cpu" and len(gpus) > 1 and "RANK" not in os.environ:
         return _spawn_local(args)

@@ -205,6 +205,72 @@ void flat_adam_ema_dev(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v, a
                  "flat_adam_ema_dev");
 }
 
+// fused Adam with lr / weight_decay per parameter group (flat_adam_groups_kernel): ema / ema_state = None: no average,
+// clip_state = None: no verdict.  chunk_group uint8[n / 64], group_state fp32[4 * G] = G x {lr, wd, 0, 0}.
+void flat_adam_groups_dev(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v, const OptT& ema, at::Tensor state,
+                          at::Tensor group_state, at::Tensor chunk_group, const OptT& ema_state,
+                          const OptT& clip_state, double beta1, double beta2, double eps, double grad_scale,
+                          double one_minus_decay, bool warmup) {
+    const char* W = "flat_adam_groups_dev";
+    check_dev(p, "param", at::kFloat);
+    check_dev(g, "grad", at::kFloat);
+    check_dev(m, "exp_avg", at::kFloat);
+    check_dev(v, "exp_avg_sq", at::kFloat);
+    check_dev(state, "state", at::kFloat);
+    check_dev(group_state, "group_state", at::kFloat);
+    check_dev(chunk_group, "chunk_group", at::kByte);
+    const int64_t n = p.numel();
+    TORCH_CHECK(n > 0 && n % 64 == 0, W, ": param has ", n, " elements, not a positive multiple of 64");
+    TORCH_CHECK(g.numel() == n && m.numel() == n && v.numel() == n && state.numel() >= 2, W, ": sizes");
+    TORCH_CHECK(chunk_group.numel() == n / 64, W, ": chunk_group has ", chunk_group.numel(), " entries, expected ",
+                n / 64, " (one per 64 elements)");
+    const int64_t G = group_state.numel() / 4;
+    TORCH_CHECK(group_state.numel() % 4 == 0 && G >= 1 && G <= 16, W, ": group_state has ", group_state.numel(),
+                " entries, expected 4 per group for 1 to 16 groups");
+    TORCH_CHECK(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) && aligned16(group_state), W,
+                ": buffers and group_state must be 16-byte aligned");
+    TORCH_CHECK(g.device() == p.device() && m.device() == p.device() && v.device() == p.device() &&
+                state.device() == p.device(), W, ": tensors on different devices");
+    TORCH_CHECK(group_state.device() == p.device(), W, ": group_state on another device");
+    TORCH_CHECK(chunk_group.device() == p.device(), W, ": chunk_group on another device");
+    TORCH_CHECK(!overlaps(chunk_group, p) && !overlaps(chunk_group, m) && !overlaps(chunk_group, v) &&
+                !overlaps(group_state, p) && !overlaps(group_state, m) && !overlaps(group_state, v),
+                W, ": chunk_group / group_state must not alias a buffer the kernel writes");
+    const float* cs = nullptr;
+    if (clip_state.has_value() && clip_state->defined()) {
+        check_clip_state(*clip_state, W);
+        TORCH_CHECK(clip_state->device() == p.device(), W, ": clip_state on another device");
+        cs = clip_state->data_ptr<float>();
+    }
+    float* e = nullptr;
+    float* es = nullptr;
+    const bool has_ema = ema.has_value() && ema->defined();
+    TORCH_CHECK(has_ema == (ema_state.has_value() && ema_state->defined()), W,
+                ": ema and ema_state go together (both or neither)");
+    if (has_ema) {
+        check_dev(*ema, "ema", at::kFloat);
+        check_dev(*ema_state, "ema_state", at::kFloat);
+        TORCH_CHECK(ema->numel() == n, W, ": sizes");
+        TORCH_CHECK(ema_state->numel() >= 4 && aligned16(*ema_state), W, ": ema_state must be fp32[4], 16-byte aligned");
+        TORCH_CHECK(aligned16(*ema), W, ": buffers must be 16-byte aligned");
+        TORCH_CHECK(ema->device() == p.device() && ema_state->device() == p.device(), W,
+                    ": tensors on different devices");
+        TORCH_CHECK(!overlaps(*ema, p) && !overlaps(*ema, g) && !overlaps(*ema, m) && !overlaps(*ema, v) &&
+                    !overlaps(*ema_state, state) && !overlaps(*ema_state, *ema) && !overlaps(*ema, chunk_group) &&
+                    !overlaps(*ema, group_state) && !overlaps(*ema_state, group_state),
+                    W, ": ema / ema_state must not alias another buffer");
+        TORCH_CHECK(one_minus_decay > 0.0 && one_minus_decay <= 1.0, W, ": one_minus_decay must be in (0, 1]");
+        e = ema->data_ptr<float>();
+        es = ema_state->data_ptr<float>();
+    }
+    check_launch(rt1_flat_adam_groups_dev(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(),
+                                          v.data_ptr<float>(), e, n, state.data_ptr<float>(),
+                                          group_state.data_ptr<float>(), chunk_group.data_ptr<uint8_t>(), (int)G, cs,
+                                          es, (float)beta1, (float)beta2, (float)eps, (float)grad_scale,
+                                          (float)one_minus_decay, warmup ? 1 : 0, cur_stream()),
+                 W);
+}
+
 // Deterministic fixed-order sum over the rows of B x [R, C] (fp32 or bf16, contiguous) -> B x [C] fp32
 // (csrc/kernels/reduce.hip).  Replaces ATen's tall-reduction path, whose cross-workgroup semaphore combine gave
 // wrong weight gradients under hipGraph replay.
@@ -1535,6 +1601,8 @@ PYBIND11_MODULE(_rt1_hip, m) {
     m.def("flat_adam_dev", &flat_adam_dev, "fused Adam/AdamW, step/lr read from a device tensor (graph-replayable)");
     m.def("flat_adam_clip_dev", &flat_adam_clip_dev, "flat_adam_dev obeying clip_state (clip coefficient, skipped step)");
     m.def("flat_adam_ema_dev", &flat_adam_ema_dev, "flat_adam_dev / flat_adam_clip_dev that also updates the EMA of the weights");
+    m.def("flat_adam_groups_dev", &flat_adam_groups_dev,
+          "the device-state Adam forms (plain, clip, EMA, both) with lr / weight_decay per parameter group");
     m.def("gradnorm_partials", &gradnorm_partials, "fp64 partial sums grad_sumsq writes for n floats");
     m.def("grad_sumsq", &grad_sumsq, "deterministic sum of squares of a flat fp32 gradient -> fp64 partials");
     m.def("grad_clip_finalize", &grad_clip_finalize, "partials -> clip_state {norm, coef, ok, counters}");

@@ -160,7 +160,103 @@ __global__ __launch_bounds__(256) void flat_adam_ema_kernel(float* __restrict__ 
     }
 }
 
+// Parameter groups: the device-state update of the three kernels above -- plain (CLIP = EMA = false), under clip_state
+// (CLIP), with the average (EMA), or both -- with lr and weight_decay PER ELEMENT.  The flat buffer pads every
+// parameter to 64 floats, so a 64-float chunk belongs to one parameter and with it to one group: chunk_group[n / 64]
+// (uint8, 1/256 B of traffic per element) names the group of each chunk, group_state fp32 [G, 4] = {lr_g, wd_g, 0, 0}
+// holds the groups' constants (G <= 16: 256 B, read straight from global memory -- every wave of the grid reads the
+// same few lines, which stay in the vector L1 / L2).  A lane's float4 i lies in chunk i >> 4, so the 16 lanes of a
+// chunk read one table byte and one float4 of constants.  t, the bias corrections and t - skipped are shared and
+// formed exactly as above; per lane a.lr = lr_g, a.weight_decay = wd_g, a.step_size = lr_g / (1 - beta1^t), then the
+// same adam_elem with the same operands: the elements of group g come out bit for bit as the ungrouped kernel of the
+// same form leaves them when it runs with (lr_g, wd_g).  A table entry >= G is read as G - 1 (never out of bounds).
+// n is a multiple of 64: there is no scalar tail.
+template <bool CLIP, bool EMA>
+__global__ __launch_bounds__(256) void flat_adam_groups_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                               float* __restrict__ m, float* __restrict__ v,
+                                                               float* __restrict__ ema, int64_t n4, AdamArgs a,
+                                                               const float* __restrict__ state,
+                                                               const float4* __restrict__ group_state,
+                                                               const uint8_t* __restrict__ chunk_group, int G,
+                                                               const float* __restrict__ clip_state,
+                                                               float* __restrict__ ema_state, float omd, int warmup) {
+    float gs = 1.f, t = state[0];
+    if (CLIP) {
+        if (clip_state[2] == 0.f) return;
+        gs = a.grad_scale;
+        a.grad_scale = clip_state[1];  // adam_elem's own multiply applies the clip coefficient second
+        t -= clip_state[3];
+    }
+    const float bc1 = -expm1f(t * logf(a.beta1));
+    a.inv_sqrt_bc2 = rsqrtf(-expm1f(t * logf(a.beta2)));
+    float omd_t = 0.f;
+    if (EMA) {
+        omd_t = warmup ? fmaxf(omd, 9.f / (10.f + t)) : omd;
+        if (blockIdx.x == 0 && threadIdx.x == 0)
+            *reinterpret_cast<float4*>(ema_state) = make_float4(omd_t, t, 0.f, 0.f);
+    }
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    float4* p4 = reinterpret_cast<float4*>(p);
+    const float4* g4 = reinterpret_cast<const float4*>(g);
+    float4* m4 = reinterpret_cast<float4*>(m);
+    float4* v4 = reinterpret_cast<float4*>(v);
+    float4* e4 = reinterpret_cast<float4*>(ema);
+    for (; i < n4; i += stride) {
+        const int gi = min((int)chunk_group[i >> 4], G - 1);
+        const float4 gc = group_state[gi];
+        a.lr = gc.x;
+        a.weight_decay = gc.y;
+        a.step_size = gc.x / bc1;
+        float4 pp = p4[i], gg = g4[i], mm = m4[i], vv = v4[i];
+        adam_elem(pp.x, pre_scale<CLIP>(gg.x, gs), mm.x, vv.x, a);
+        adam_elem(pp.y, pre_scale<CLIP>(gg.y, gs), mm.y, vv.y, a);
+        adam_elem(pp.z, pre_scale<CLIP>(gg.z, gs), mm.z, vv.z, a);
+        adam_elem(pp.w, pre_scale<CLIP>(gg.w, gs), mm.w, vv.w, a);
+        p4[i] = pp; m4[i] = mm; v4[i] = vv;
+        if (EMA) {
+            float4 ee = e4[i];
+            ee.x = fmaf(omd_t, pp.x - ee.x, ee.x);
+            ee.y = fmaf(omd_t, pp.y - ee.y, ee.y);
+            ee.z = fmaf(omd_t, pp.z - ee.z, ee.z);
+            ee.w = fmaf(omd_t, pp.w - ee.w, ee.w);
+            e4[i] = ee;
+        }
+    }
+}
+
+template <bool CLIP, bool EMA>
+void launch_groups(unsigned blocks, hipStream_t stream, float* p, const float* g, float* m, float* v, float* ema,
+                   int64_t n4, const AdamArgs& a, const float* state, const float* group_state,
+                   const uint8_t* chunk_group, int G, const float* clip_state, float* ema_state, float omd,
+                   int warmup) {
+    hipLaunchKernelGGL((flat_adam_groups_kernel<CLIP, EMA>), dim3(blocks), dim3(256), 0, stream, p, g, m, v, ema, n4, a,
+                       state, reinterpret_cast<const float4*>(group_state), chunk_group, G, clip_state, ema_state, omd,
+                       warmup);
+}
+
 }  // namespace
+
+// ema == nullptr: no average (ema_state unused); clip_state == nullptr: no verdict to obey.  n % 64 == 0, 1 <= G <= 16.
+extern "C" int rt1_flat_adam_groups_dev(float* p, const float* g, float* m, float* v, float* ema, int64_t n,
+                                        const float* state, const float* group_state, const uint8_t* chunk_group,
+                                        int G, const float* clip_state, float* ema_state, float beta1, float beta2,
+                                        float eps, float grad_scale, float one_minus_decay, int warmup,
+                                        hipStream_t stream) {
+    if (state == nullptr || group_state == nullptr || chunk_group == nullptr || n <= 0 || n % 64 != 0 || G < 1 ||
+        G > 16 || (ema != nullptr && ema_state == nullptr))
+        return (int)hipErrorInvalidValue;
+    AdamArgs a{0.f, beta1, beta2, eps, 0.f, 0.f, 1.f, grad_scale};
+    const int64_t n4 = n / 4;
+    int64_t blocks = (n4 + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    const bool clip = clip_state != nullptr, avg = ema != nullptr;
+    auto* fn = clip ? (avg ? launch_groups<true, true> : launch_groups<true, false>)
+                    : (avg ? launch_groups<false, true> : launch_groups<false, false>);
+    fn((unsigned)blocks, stream, p, g, m, v, ema, n4, a, state, group_state, chunk_group, G, clip_state, ema_state,
+       one_minus_decay, warmup);
+    return (int)hipGetLastError();
+}
 
 extern "C" int rt1_flat_adam_ema_dev(float* p, const float* g, float* m, float* v, float* ema, int64_t n,
                                      const float* state, const float* clip_state, float* ema_state, float beta1,

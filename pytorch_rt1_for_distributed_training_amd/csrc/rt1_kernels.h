@@ -25,6 +25,13 @@ int rt1_flat_adam_ema_dev(float* p, const float* g, float* m, float* v, float* e
                           const float* clip_state, float* ema_state, float beta1, float beta2, float eps,
                           float weight_decay, float grad_scale, float one_minus_decay, int warmup,
                           hipStream_t stream);
+// the device-state update with lr and weight_decay per parameter group: chunk_group uint8[n / 64] names the group of
+// each 64-float chunk, group_state fp32 [G, 4] = {lr_g, wd_g, 0, 0}, 1 <= G <= 16, n % 64 == 0.  ema == nullptr:
+// no average; clip_state == nullptr: no verdict.  Group g's elements equal the ungrouped kernel's at (lr_g, wd_g).
+int rt1_flat_adam_groups_dev(float* p, const float* g, float* m, float* v, float* ema, int64_t n, const float* state,
+                             const float* group_state, const uint8_t* chunk_group, int G, const float* clip_state,
+                             float* ema_state, float beta1, float beta2, float eps, float grad_scale,
+                             float one_minus_decay, int warmup, hipStream_t stream);
 
 // gradnorm.hip (deterministic global gradient norm -> clip_state fp32[8] = {norm, coef, ok, skipped steps, clipped
 // steps, consecutive skipped steps, 0, 0}; rt1_gradnorm_partials: workgroups / fp64 partials for n floats, a function

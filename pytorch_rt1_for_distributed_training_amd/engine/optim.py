@@ -9,19 +9,34 @@ same update but owns flat fp32 moment buffers aligned with
 gradient average into that pass.  AdamW is the same kernel with decoupled
 decay (``weight_decay > 0``); the default 0 keeps parity with the reference.
 
-It subclasses ``torch.optim.Optimizer`` so torch LR schedulers drive
-``param_groups[0]['lr']`` and ``state_dict()`` is emitted in torch-Adam layout
-(per-parameter ``step``/``exp_avg``/``exp_avg_sq``) for Lightning-format
-checkpoints.
+It subclasses ``torch.optim.Optimizer`` so torch LR schedulers drive every
+group's ``lr`` and ``state_dict()`` is emitted in torch-Adam layout
+(per-parameter ``step``/``exp_avg``/``exp_avg_sq``, one entry per group) for
+Lightning-format checkpoints.
+
+Parameter groups (``groups=[{"params", "name", "lr", "weight_decay"}, ...]``, at
+most 16): the groups are scattered through the gradient-ready-order flat buffer,
+so the group is looked up per 64-element chunk inside the one launch
+(``ops.adam.flat_adam_groups_dev_step``: ``chunk_group`` uint8 per chunk,
+``group_state`` fp32 ``[G, 4] = {lr, wd, 0, 0}`` on the device).  While every group
+holds the same ``(lr, weight_decay)`` -- the single default group always does --
+the step runs the ungrouped kernels, to which the grouped one is bitwise equal
+group by group; a capture with more than one group always records the grouped
+kernel, so a later scheduler step cannot invalidate the graph.
+``build_param_groups`` makes the usual groups from a model: no weight decay on
+norms, biases and embeddings, a smaller learning rate on the pretrained backbone.
 """
 from __future__ import annotations
 
 import math
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
-from ..parallel.flat import FlatParameters
+from ..parallel.flat import ALIGN, FlatParameters
+
+MAX_GROUPS = 16          # ops.adam.MAX_GROUPS: group_state is at most [16, 4]
+DEFAULT_GROUP = "all"    # how an unnamed group (the single default one) is called in lrs / layouts
 
 
 class FlatAdam(torch.optim.Optimizer):
@@ -29,21 +44,37 @@ class FlatAdam(torch.optim.Optimizer):
                  weight_decay: float = 0.0, all_params: Optional[Sequence[torch.nn.Parameter]] = None,
                  use_kernel: Optional[bool] = None, max_grad_norm: Optional[float] = None,
                  skip_nonfinite: bool = False, ema_decay: float = 0.0, ema_warmup: bool = True,
-                 param_names: Optional[Dict[int, str]] = None):
+                 param_names: Optional[Dict[int, str]] = None, groups: Optional[Sequence[dict]] = None):
         if not 0.0 <= float(ema_decay) < 1.0:
             raise ValueError(f"ema_decay must be in [0, 1) (0 = off), got {ema_decay!r}")
         self.flat = flat
         params = list(all_params) if all_params is not None else list(flat.params)
+        decoupled = weight_decay > 0
+        if groups is not None:
+            params = self._checked_groups(groups, params)
+            decoupled = any(g.get("weight_decay", weight_decay) > 0 for g in params)
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False,
                                       maximize=False, foreach=None, capturable=False, differentiable=False,
-                                      fused=None, decoupled_weight_decay=weight_decay > 0))
+                                      fused=None, decoupled_weight_decay=decoupled))
         self.exp_avg = torch.zeros_like(flat.data)
         self.exp_avg_sq = torch.zeros_like(flat.data)
         self.step_count = 0
-        # device-resident step counter + lr so a captured graph replays correctly
+        # device-resident step counter + group 0's lr so a captured graph replays correctly
         self.dev_state = torch.zeros(2, dtype=torch.float32, device=flat.data.device)
-        self._dev_lr = None
+        self._dev_groups = None     # ((lr, weight_decay), ...) per group as last written to the device
         self._dev_step = None
+        # more than one group: the group of every 64-element chunk of the flat buffer (a parameter's padding belongs
+        # to it; frozen parameters have no chunks) and the groups' {lr, wd, 0, 0} on the device
+        self.chunk_group = self.group_state = None
+        self._elem_cache = None     # CPU / no-kernel path: (host groups, lr per element, wd per element)
+        if len(self.param_groups) > 1:
+            group_of = {id(p): gi for gi, g in enumerate(self.param_groups) for p in g["params"]}
+            table = torch.zeros(flat.numel // ALIGN, dtype=torch.uint8)
+            ends = list(flat.offsets[1:]) + [flat.numel]
+            for p, o, e in zip(flat.params, flat.offsets, ends):
+                table[o // ALIGN:e // ALIGN] = group_of[id(p)]
+            self.chunk_group = table.to(flat.data.device)
+            self.group_state = torch.zeros(len(self.param_groups), 4, dtype=torch.float32, device=flat.data.device)
         self._kernel = None
         if use_kernel is None:
             use_kernel = flat.data.is_cuda
@@ -83,21 +114,33 @@ class FlatAdam(torch.optim.Optimizer):
         loss = closure() if closure is not None else None
         g = self.param_groups[0]
         lr, (b1, b2), eps, wd = g["lr"], g["betas"], g["eps"], g["weight_decay"]
+        capturing = self._kernel is not None and torch.cuda.is_current_stream_capturing()
+        # {step, lr} (and every group's {lr, wd}) live on the device and the step is advanced by a device op, so the
+        # eager step and a captured hipGraph replay run the identical kernel (the host writes them only when they
+        # are out of date, e.g. after an lr-scheduler step -- never inside a capture)
+        if self._kernel is not None and not capturing and self.device_state_stale():
+            self.sync_device_state()
         self.step_count += 1
         t = self.step_count
         self.flat.gather_grads()
+        # the route: the ungrouped kernels while all groups hold one (lr, wd); a capture with several groups always
+        # records the grouped kernel (the graph outlives the next scheduler step)
+        grouped = len(self.param_groups) > 1 and (capturing or not self.groups_uniform())
         if self._kernel is not None:
-            # {step, lr} live on the device and the step is advanced by a device op, so the eager step and a
-            # captured hipGraph replay run the identical kernel (the host writes dev_state only when it is
-            # out of date, e.g. after an lr-scheduler step -- never inside a capture)
-            if not torch.cuda.is_current_stream_capturing() and (self._dev_step != t - 1 or self._dev_lr != lr):
-                self.write_device_state(t - 1, lr)
             self.dev_state[0:1].add_(1.0)
             self._dev_step = t
             if self.clip_enabled:
                 self._kernel.grad_norm_clip_(self.flat.grad, self.clip_state, self._partials,
                                              max_norm=self.max_grad_norm, grad_scale=grad_scale,
                                              skip_nonfinite=self.skip_nonfinite)
+            if grouped:
+                self._kernel.flat_adam_groups_dev_step(self.flat.data, self.flat.grad, self.exp_avg, self.exp_avg_sq,
+                                                       self.dev_state, self.group_state, self.chunk_group,
+                                                       ema=self.ema, ema_state=self.ema_state,
+                                                       clip_state=self.clip_state, beta1=b1, beta2=b2, eps=eps,
+                                                       grad_scale=grad_scale, one_minus_decay=self._omd,
+                                                       warmup=self.ema_warmup)
+                return loss
             if self.ema_enabled:
                 self._kernel.flat_adam_ema_dev_step(self.flat.data, self.flat.grad, self.exp_avg, self.exp_avg_sq,
                                                     self.ema, self.dev_state, self.ema_state, self.clip_state,
@@ -126,14 +169,20 @@ class FlatAdam(torch.optim.Optimizer):
                 grad = grad * coef
             t -= self.skipped_steps
         p = self.flat.data
-        if wd:
+        if grouped:
+            lr_e, wd_e = self._per_element()         # the same update with lr and wd expanded per element
+            p.mul_(1.0 - lr_e * wd_e)
+        elif wd:
             p.mul_(1.0 - lr * wd)
         self.exp_avg.lerp_(grad, 1.0 - b1)
         self.exp_avg_sq.mul_(b2).addcmul_(grad, grad, value=1.0 - b2)
         bc1 = 1.0 - b1 ** t
         bc2 = 1.0 - b2 ** t
         denom = (self.exp_avg_sq.sqrt() / math.sqrt(bc2)).add_(eps)
-        p.addcdiv_(self.exp_avg, denom, value=-lr / bc1)
+        if grouped:
+            p.sub_((lr_e / bc1) * (self.exp_avg / denom))
+        else:
+            p.addcdiv_(self.exp_avg, denom, value=-lr / bc1)
         if self.ema_enabled:
             # the kernel's recurrence in torch: omd_t in fp32 from the same t, ema += omd_t * (p - ema)
             omd_t = self._omd_t(t)
@@ -226,14 +275,76 @@ class FlatAdam(torch.optim.Optimizer):
                 pos.setdefault(id(p), len(pos))
         return [str(pos[id(p)]) for p in self.flat.params]
 
-    def write_device_state(self, step: int, lr: float):
-        """Host -> device write of {step, lr} (a small H2D copy; outside any capture)."""
-        self.dev_state.copy_(torch.tensor([float(step), float(lr)]))
+    # -------------------------------------------------------------- parameter groups
+    @staticmethod
+    def _checked_groups(groups: Sequence[dict], all_params: List[torch.nn.Parameter]) -> List[dict]:
+        """``groups`` as torch param-group dicts, after checking that they partition ``all_params``."""
+        groups = [dict(g, params=list(g["params"])) for g in groups]
+        if not 1 <= len(groups) <= MAX_GROUPS:
+            raise ValueError(f"FlatAdam takes 1 to {MAX_GROUPS} parameter groups, got {len(groups)}")
+        seen: Dict[int, int] = {}
+        for gi, g in enumerate(groups):
+            extra = set(g) - {"params", "name", "lr", "weight_decay"}
+            if extra:
+                raise ValueError(f"parameter group {gi} has unknown keys {sorted(extra)}")
+            for p in g["params"]:
+                if id(p) in seen:
+                    raise ValueError(f"a parameter of shape {tuple(p.shape)} is in two parameter groups "
+                                     f"({seen[id(p)]} and {gi})")
+                seen[id(p)] = gi
+        missing = [p for p in all_params if id(p) not in seen]
+        if missing:
+            raise ValueError(f"{len(missing)} parameters are in no parameter group, e.g. one of shape "
+                             f"{tuple(missing[0].shape)}")
+        if len(seen) != len(all_params):
+            raise ValueError(f"the parameter groups hold {len(seen) - len(all_params)} parameters that are not the "
+                             f"optimizer's")
+        return groups
+
+    def host_groups(self) -> Tuple[Tuple[float, float], ...]:
+        """``(lr, weight_decay)`` of every group as the host holds them now."""
+        return tuple((float(g["lr"]), float(g["weight_decay"])) for g in self.param_groups)
+
+    def groups_uniform(self) -> bool:
+        hg = self.host_groups()
+        return all(x == hg[0] for x in hg)
+
+    @property
+    def group_names(self) -> List[str]:
+        return [g.get("name", DEFAULT_GROUP) for g in self.param_groups]
+
+    def group_layout(self, groups: Optional[Sequence[dict]] = None) -> List[Tuple[str, int]]:
+        """``[(name, number of parameters)]`` of this optimizer's groups, or of a ``state_dict()``'s."""
+        groups = self.param_groups if groups is None else groups
+        return [(g.get("name", DEFAULT_GROUP), len(g["params"])) for g in groups]
+
+    def _per_element(self):
+        """CPU / no-kernel path: fp32 ``lr`` and ``weight_decay`` per flat element, rebuilt when a group changes."""
+        hg = self.host_groups()
+        if self._elem_cache is None or self._elem_cache[0] != hg:
+            idx = self.chunk_group.long().repeat_interleave(ALIGN)
+            dev = self.flat.data.device
+            self._elem_cache = (hg, torch.tensor([x[0] for x in hg], dtype=torch.float32, device=dev)[idx],
+                                torch.tensor([x[1] for x in hg], dtype=torch.float32, device=dev)[idx])
+        return self._elem_cache[1], self._elem_cache[2]
+
+    def device_state_stale(self) -> bool:
+        """Whether the device copies of the step and of any group's ``(lr, weight_decay)`` differ from the host's
+        (an lr-scheduler step, a loaded checkpoint, an eager step the device did not count)."""
+        return self._dev_step != self.step_count or self._dev_groups != self.host_groups()
+
+    def write_device_state(self, step: int):
+        """Host -> device write of {step, group 0's lr} and, with several groups, of every group's {lr, wd, 0, 0}
+        (small H2D copies; outside any capture)."""
+        hg = self.host_groups()
+        self.dev_state.copy_(torch.tensor([float(step), hg[0][0]]))
+        if self.group_state is not None:
+            self.group_state.copy_(torch.tensor([[x[0], x[1], 0.0, 0.0] for x in hg], dtype=torch.float32))
         self._dev_step = int(step)
-        self._dev_lr = float(lr)
+        self._dev_groups = hg
 
     def sync_device_state(self):
-        self.write_device_state(self.step_count, self.param_groups[0]["lr"])
+        self.write_device_state(self.step_count)
 
     def zero_grad(self, set_to_none: bool = True):
         self.flat.zero_grad(set_to_none)
@@ -263,6 +374,14 @@ class FlatAdam(torch.optim.Optimizer):
 
     def load_state_dict(self, sd: Dict):
         groups = sd["param_groups"]
+        # torch's own refusals, with both layouts named: a checkpoint's groups must be this optimizer's
+        if len(groups) != len(self.param_groups):
+            raise ValueError(f"loaded state dict has a different number of parameter groups: it holds "
+                             f"{self.group_layout(groups)}, the optimizer {self.group_layout()}")
+        if any(len(sg["params"]) != len(g["params"]) or
+               ("name" in sg and sg["name"] != g.get("name", sg["name"])) for g, sg in zip(self.param_groups, groups)):
+            raise ValueError(f"loaded state dict contains a parameter group that doesn't match the optimizer's: it "
+                             f"holds {self.group_layout(groups)}, the optimizer {self.group_layout()}")
         for g, sg in zip(self.param_groups, groups):
             for k, v in sg.items():
                 if k != "params":
@@ -285,6 +404,49 @@ class FlatAdam(torch.optim.Optimizer):
         if self.clip_state is not None:
             self.clip_state.zero_()      # the host counter is the effective step again
             self._dev_step = None
+
+
+def backbone_parameters(model: torch.nn.Module) -> List[torch.nn.Parameter]:
+    """The parameters a pretrained EfficientNet-B3 state dict fills (``models.efficientnet.pretrained_keys``, the list
+    the loader itself walks), over every ``FiLMEfficientNet`` inside ``model``, in module order."""
+    from ..models.efficientnet import FiLMEfficientNet, pretrained_keys
+    out = []
+    for mod in model.modules():
+        if isinstance(mod, FiLMEfficientNet):
+            named = dict(mod.named_parameters())
+            out += [named[k] for k in pretrained_keys(mod) if k in named]
+    return out
+
+
+def build_param_groups(model: torch.nn.Module, lr: float, weight_decay: float, no_decay_norm_bias: bool = False,
+                       backbone_lr_mult: float = 1.0) -> List[dict]:
+    """The parameter groups of ``FlatAdam(groups=...)`` for ``model``, from names and module types alone (the same on
+    every rank), every parameter -- frozen ones included -- in exactly one group, in ``model.parameters()`` order:
+
+    * ``no_decay_norm_bias``: parameters with ``ndim <= 1`` (BatchNorm / LayerNorm scales and shifts, every conv and
+      linear bias) and ``nn.Embedding`` weights get ``weight_decay = 0``;
+    * ``backbone_lr_mult != 1``: the pretrained backbone (``backbone_parameters``; the FiLM layers are not in it)
+      gets ``lr * backbone_lr_mult``.
+
+    The two rules cross to at most four groups, ``new``, ``new_no_decay``, ``backbone``, ``backbone_no_decay``; empty
+    ones are dropped.  With both rules off: the one unnamed group of ``FlatAdam`` without ``groups``."""
+    if not backbone_lr_mult > 0:
+        raise ValueError(f"backbone_lr_mult must be > 0, got {backbone_lr_mult!r}")
+    params = list(model.parameters())
+    split_lr = float(backbone_lr_mult) != 1.0
+    if not no_decay_norm_bias and not split_lr:
+        return [dict(params=params, lr=lr, weight_decay=weight_decay)]
+    backbone = {id(p) for p in backbone_parameters(model)} if split_lr else set()
+    embeddings = {id(m.weight) for m in model.modules() if isinstance(m, torch.nn.Embedding)}
+    groups = {name: dict(name=name, params=[], lr=lr * (backbone_lr_mult if name.startswith("backbone") else 1.0),
+                         weight_decay=0.0 if name.endswith("no_decay") else weight_decay)
+              for name in ("new", "new_no_decay", "backbone", "backbone_no_decay")}
+    for p in params:
+        name = "backbone" if id(p) in backbone else "new"
+        if no_decay_norm_bias and (p.ndim <= 1 or id(p) in embeddings):
+            name += "_no_decay"
+        groups[name]["params"].append(p)
+    return [g for g in groups.values() if g["params"]]
 
 
 def multistep_lr(optimizer: torch.optim.Optimizer, milestones: List[int], gamma: float = 0.1):

@@ -45,6 +45,14 @@ every step path above carries it and a skipped step leaves it untouched.  BN run
 (``torch.optim.swa_utils.AveragedModel``'s default).  The buffer is fp32: at decay 0.9999 an update whose ``|p - ema|`` is
 below about ``1e-3 |ema|`` moves it by less than an ulp.
 
+``no_decay_norm_bias`` / ``backbone_lr_mult`` (off / 1, and then nothing here changes): the optimizer gets up to four
+parameter groups (``engine.optim.build_param_groups``: no weight decay on norms, biases and embeddings; a smaller
+learning rate on the pretrained backbone) and the Adam launch looks the group up per 64-element chunk
+(``ops.adam.flat_adam_groups_dev_step``), on every step path above and together with clipping and the EMA.  Each group's
+``{lr, wd}`` is device state like the step: a scheduler step rewrites it from the host before the next replay, so the
+captured graph stays valid.  ``backbone_lr_mult != 1`` asks for pretrained weights (``pretrained``, else the model's
+``backbone_pretrained`` mark that ``models.load_pretrained_backbone`` leaves).  ``lrs`` gives every group's lr by name.
+
 No ``network_state`` is fabricated (the reference samples a random one on the
 CPU and copies it to the GPU every step only to read its shape).
 """
@@ -62,7 +70,7 @@ from ..parallel import dist as pdist
 from ..parallel.ddp import DataParallel, gradient_ready_order
 from ..parallel.flat import deferred_sums
 from ..parallel.flat import FlatParameters
-from .optim import FlatAdam, multistep_lr
+from .optim import FlatAdam, build_param_groups, multistep_lr
 
 
 def split_batch(batch: Dict) -> tuple:
@@ -131,7 +139,17 @@ class TrainEngine:
                  broadcast_buffers: bool = True, device: Optional[torch.device] = None,
                  grad_comm_dtype: torch.dtype = torch.float32, order_probe: bool = True, comm: str = "torch",
                  graph: bool = False, max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False,
-                 accumulate_grad_batches: int = 1, ema_decay: float = 0.0, ema_warmup: bool = True):
+                 accumulate_grad_batches: int = 1, ema_decay: float = 0.0, ema_warmup: bool = True,
+                 no_decay_norm_bias: bool = False, backbone_lr_mult: float = 1.0,
+                 pretrained: Optional[bool] = None):
+        if not isinstance(backbone_lr_mult, (int, float)) or not backbone_lr_mult > 0:
+            raise ValueError(f"backbone_lr_mult must be a number > 0, got {backbone_lr_mult!r}")
+        if pretrained is None:
+            pretrained = bool(getattr(model, "backbone_pretrained", False))
+        if float(backbone_lr_mult) != 1.0 and not pretrained:
+            raise ValueError(f"backbone_lr_mult={backbone_lr_mult} needs pretrained weights to protect: load them "
+                             f"(--pretrained, models.load_pretrained_backbone) or resume a checkpoint (--resume; "
+                             f"pretrained=True)")
         if int(accumulate_grad_batches) != accumulate_grad_batches or accumulate_grad_batches < 1:
             raise ValueError(f"accumulate_grad_batches must be an integer >= 1, got {accumulate_grad_batches!r}")
         ctx = pdist.context()
@@ -170,10 +188,16 @@ class TrainEngine:
             raise ValueError(f"unknown comm backend {comm!r}")
         self.ddp = DataParallel(self.model, self.flat, bucket_cap_mb=bucket_cap_mb,
                                 broadcast_buffers=broadcast_buffers, grad_comm_dtype=grad_comm_dtype, comm=native)
+        # parameter groups (engine/optim.py build_param_groups); with both rules off the one default group, and then
+        # nothing here changes
+        groups = None
+        if no_decay_norm_bias or float(backbone_lr_mult) != 1.0:
+            groups = build_param_groups(self.model, lr, weight_decay, bool(no_decay_norm_bias),
+                                        float(backbone_lr_mult))
         self.optimizer = FlatAdam(self.flat, lr=lr, weight_decay=weight_decay,
                                   all_params=list(self.model.parameters()), max_grad_norm=max_grad_norm,
                                   skip_nonfinite=skip_nonfinite, ema_decay=ema_decay, ema_warmup=ema_warmup,
-                                  param_names={id(p): n for n, p in self.model.named_parameters()})
+                                  param_names={id(p): n for n, p in self.model.named_parameters()}, groups=groups)
         # skip_nonfinite: the forward of a bad batch has already written the BN running statistics when the norm
         # kernel notices, so they live in one flat buffer (the data-parallel one when there is one) with a shadow copy
         # of the last good state; buffer_guard_ advances or rolls back right after the optimizer step
@@ -382,7 +406,7 @@ class TrainEngine:
             return loss
         _copy_into(self._static_batch, batch)
         opt = self.optimizer
-        if opt._dev_lr != float(opt.param_groups[0]["lr"]) or opt._dev_step != opt.step_count:
+        if opt.device_state_stale():
             opt.sync_device_state()
         self._graph.replay()
         opt.step_count += 1
@@ -565,7 +589,9 @@ class TrainEngine:
         opt = self.optimizer
         with torch.no_grad():
             return dict(data=self.flat.data.clone(), m=opt.exp_avg.clone(), v=opt.exp_avg_sq.clone(),
-                        dev=opt.dev_state.clone(), step=opt.step_count, dev_step=opt._dev_step, dev_lr=opt._dev_lr,
+                        dev=opt.dev_state.clone(), step=opt.step_count, dev_step=opt._dev_step,
+                        dev_groups=opt._dev_groups,
+                        group_state=(opt.group_state.clone() if opt.group_state is not None else None),
                         bufs=[b.detach().clone() for b in self.model.buffers()],
                         rng=(torch.cuda.get_rng_state(self.device) if self.device.type == "cuda" else None),
                         cpu_rng=torch.get_rng_state(),
@@ -586,6 +612,8 @@ class TrainEngine:
             opt.exp_avg.copy_(s["m"])
             opt.exp_avg_sq.copy_(s["v"])
             opt.dev_state.copy_(s["dev"])
+            if s["group_state"] is not None:
+                opt.group_state.copy_(s["group_state"])
             for b, c in zip(self.model.buffers(), s["bufs"]):
                 b.copy_(c)
             for d, t in s["ctr"].items():
@@ -600,7 +628,7 @@ class TrainEngine:
                 opt.ema.copy_(s["ema"])
                 opt.ema_state.copy_(s["ema_state"])
         self.micro_step, self.stepped = s["micro"], s["stepped"]
-        opt.step_count, opt._dev_step, opt._dev_lr = s["step"], s["dev_step"], s["dev_lr"]
+        opt.step_count, opt._dev_step, opt._dev_groups = s["step"], s["dev_step"], s["dev_groups"]
         if s["rng"] is not None:
             torch.cuda.set_rng_state(s["rng"], self.device)
         torch.set_rng_state(s["cpu_rng"])
@@ -683,3 +711,8 @@ class TrainEngine:
     @property
     def lr(self) -> float:
         return self.optimizer.param_groups[0]["lr"]
+
+    @property
+    def lrs(self) -> Dict[str, float]:
+        """Learning rate of every parameter group by name (``lr`` is the first group's)."""
+        return {n: g["lr"] for n, g in zip(self.optimizer.group_names, self.optimizer.param_groups)}

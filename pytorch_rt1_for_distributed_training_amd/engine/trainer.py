@@ -28,6 +28,10 @@ validation, the LR scheduler and checkpointing, so no checkpoint ever holds a ha
 With the engine's ``ema_decay > 0`` every validation also runs on the averaged weights and logs ``eval_loss_ema``,
 checkpoints carry the average under one more top-level key, ``"ema"``, and ``resume`` restores it (or starts it at the
 restored weights when the checkpoint has none).  ``eval_loss`` and the checkpoint file names are those of the live weights.
+
+With more than one parameter group (the engine's ``no_decay_norm_bias`` / ``backbone_lr_mult``) each epoch also logs
+``lr/<group>``; checkpoints carry the groups in the optimizer and scheduler states, and ``resume`` restores their names
+and learning rates -- into the same group layout only: the resumed run's flags must reproduce it.
 """
 from __future__ import annotations
 
@@ -131,7 +135,12 @@ class Trainer:
         ck = load_checkpoint(path, map_location="cpu")
         load_model_state(self.engine.model, ck)
         if ck.get("optimizer_states"):
-            self.engine.optimizer.load_state_dict(ck["optimizer_states"][0])
+            opt, saved = self.engine.optimizer, ck["optimizer_states"][0]
+            if opt.group_layout(saved["param_groups"]) != opt.group_layout():
+                raise ValueError(f"{path} was written with the parameter groups (name, parameters) "
+                                 f"{opt.group_layout(saved['param_groups'])}, this run has {opt.group_layout()}: "
+                                 f"resume with the --no_decay_norm_bias / --backbone_lr_mult of the run that wrote it")
+            opt.load_state_dict(saved)
         if ck.get("lr_schedulers"):
             self.engine.scheduler.load_state_dict(ck["lr_schedulers"][0])
         self.engine.global_step = int(ck.get("global_step", 0))
@@ -205,6 +214,8 @@ class Trainer:
             elif hasattr(train_loader, "set_epoch"):
                 train_loader.set_epoch(epoch)
             self._log({"lr-Adam": e.lr})
+            if len(e.lrs) > 1:
+                self._log({f"lr/{name}": v for name, v in e.lrs.items()})
             total, n, window, wn = None, 0, None, 0
             wsteps = 0                               # optimizer steps since the last log point (wn counts batches)
             samples = 0

@@ -68,4 +68,5 @@ def load_pretrained_backbone(model: TransformerNetwork, path_or_state) -> Transf
         if isinstance(sd, dict) and "state_dict" in sd and isinstance(sd["state_dict"], dict):
             sd = sd["state_dict"]
     load_torchvision_b3_state_dict(model._image_tokenizer._tokenizer.net, sd)
+    model.backbone_pretrained = True      # TrainEngine(backbone_lr_mult=...) asks for pretrained weights to protect
     return model

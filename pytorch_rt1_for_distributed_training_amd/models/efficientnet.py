@@ -249,13 +249,21 @@ class FiLMEfficientNet(nn.Module):
         return x
 
 
+def pretrained_keys(model: FiLMEfficientNet) -> List[str]:
+    """The ``state_dict()`` entries of ``model`` (parameters and BN buffers, in order) that a torchvision
+    ``efficientnet_b3`` state dict fills: everything but the FiLM layers.  The one definition of "the pretrained
+    backbone": ``load_torchvision_b3_state_dict`` loads exactly these and ``engine.optim.build_param_groups`` gives
+    exactly their parameters the backbone learning rate."""
+    return [k for k in model.state_dict() if not k.startswith("films.")]
+
+
 def load_torchvision_b3_state_dict(model: FiLMEfficientNet, official_state_dict) -> FiLMEfficientNet:
     """Map a torchvision ``efficientnet_b3`` state dict onto a FiLM-free
     backbone *positionally*, like ``load_official_pytorch_param``
     (``film_efficientnet_encoder.py:411-425``).  FiLM layers keep their
     zero init.  Load the file with ``torch.load(..., weights_only=True)``."""
     target = model.state_dict()
-    keys = [k for k in target if not k.startswith("films.")]
+    keys = pretrained_keys(model)
     src = list(official_state_dict.values())
     if len(src) < len(keys):
         raise ValueError(f"official state dict has {len(src)} tensors, backbone needs {len(keys)}")

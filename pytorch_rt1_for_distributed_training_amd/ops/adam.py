@@ -65,6 +65,41 @@ def flat_adam_ema_dev_step(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v:
                              grad_scale, float(one_minus_decay), bool(warmup))
 
 
+CHUNK = 64             # floats per chunk_group entry: parallel.flat.ALIGN, so a chunk lies inside one parameter
+MAX_GROUPS = 16
+GROUP_STATE_SLOTS = 4  # {lr, weight_decay, 0, 0} per group
+
+
+def flat_adam_groups_dev_step(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, state: torch.Tensor,
+                              group_state: torch.Tensor, chunk_group: torch.Tensor, *, ema: torch.Tensor = None,
+                              ema_state: torch.Tensor = None, clip_state: torch.Tensor = None, beta1: float,
+                              beta2: float, eps: float, grad_scale: float = 1.0, one_minus_decay: float = 1.0,
+                              warmup: bool = True):
+    """The device-state update with ``lr`` and ``weight_decay`` per parameter group, in one launch: ``chunk_group``
+    uint8[n / 64] names the group of each 64-float chunk and ``group_state`` fp32[G, 4] holds ``{lr_g, wd_g, 0, 0}``
+    (``G <= 16``).  The form follows the arguments like the ungrouped ops: ``flat_adam_dev_step`` (neither),
+    ``flat_adam_clip_dev_step`` (``clip_state``), ``flat_adam_ema_dev_step`` (``ema`` and ``ema_state``, with or
+    without ``clip_state``).  The elements of group ``g`` come out bit for bit as that op leaves them when it runs
+    over the whole buffer with ``(lr_g, wd_g)``; ``state[1]`` (the ungrouped lr) is not read."""
+    load().flat_adam_groups_dev(p, g, m, v, ema, state, group_state, chunk_group, ema_state, clip_state, beta1, beta2,
+                                eps, grad_scale, float(one_minus_decay), bool(warmup))
+
+
+def reference_adam_groups_step(p, g, m, v, chunk_group, group_lr, group_wd, *, beta1, beta2, eps, step,
+                               grad_scale=1.0):
+    """Plain PyTorch oracle of the grouped update in the dtype of its operands (fp64 for a referee): the math of
+    ``reference_adam_step`` with ``lr`` and ``weight_decay`` expanded per element from ``chunk_group``."""
+    idx = chunk_group.to(device=p.device, dtype=torch.long).repeat_interleave(CHUNK)
+    lr = torch.as_tensor(group_lr, dtype=p.dtype, device=p.device)[idx]
+    wd = torch.as_tensor(group_wd, dtype=p.dtype, device=p.device)[idx]
+    g = g * grad_scale
+    p.mul_(1 - lr * wd)
+    m.mul_(beta1).add_(g, alpha=1 - beta1)
+    v.mul_(beta2).addcmul_(g, g, value=1 - beta2)
+    denom = (v.sqrt() / math.sqrt(1 - beta2 ** step)).add_(eps)
+    p.sub_(lr / (1 - beta1 ** step) * (m / denom))
+
+
 def reference_ema_step(ema: torch.Tensor, p: torch.Tensor, omd_t) -> torch.Tensor:
     """fp64 oracle of one EMA update, ``ema + omd_t * (p - ema)``; returns fp64 and modifies nothing."""
     e = ema.double()
