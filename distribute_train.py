@@ -24,6 +24,36 @@ import subprocess
 import sys
 
 
+LR_SCHEDULES = ("constant", "linear", "cosine", "rsqrt")
+DEFAULT_MILESTONES = [50, 75, 90]
+
+
+def resolve_milestones(args):
+    """--milestones as given; left out: the reference's 50 75 90, or none under a decaying --lr_schedule."""
+    if args.milestones is not None:
+        return list(args.milestones)
+    return list(DEFAULT_MILESTONES) if args.lr_schedule in ("none", "constant") else []
+
+
+def resolve_lr_schedule(args, train_loader=None):
+    """The engine's ``lr_schedule`` dict (None for ``none``).  ``--lr_decay_steps 0`` with linear / cosine means the
+    whole run, which needs the number of batches per epoch: a loader without a length is refused."""
+    if args.lr_schedule == "none":
+        return None
+    decay = int(args.lr_decay_steps)
+    if decay == 0 and args.lr_schedule in ("linear", "cosine"):
+        try:
+            batches = len(train_loader)
+        except TypeError:
+            raise SystemExit(f"--lr_schedule {args.lr_schedule} with --lr_decay_steps 0 needs the length of the "
+                             f"training loader, and this one has none: pass --lr_decay_steps")
+        if args.limit_train_batches is not None:
+            batches = min(batches, args.limit_train_batches)
+        decay = args.max_epochs * -(-batches // args.accumulate_grad_batches)
+    return dict(kind=args.lr_schedule, warmup_steps=int(args.warmup_steps), decay_steps=decay,
+                min_lr_ratio=float(args.min_lr_ratio))
+
+
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     # ---- reference flags
@@ -32,7 +62,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--max_epochs", type=int, default=100)
     p.add_argument("--batch_size", type=int, default=8)
     p.add_argument("--num_workers", type=int, default=15)
-    p.add_argument("--milestones", type=int, nargs="+", default=[50, 75, 90])
+    p.add_argument("--milestones", type=int, nargs="+", default=None,
+                   help="epochs at which MultiStepLR multiplies every lr by 0.1 (default: 50 75 90, or none with a "
+                        "decaying --lr_schedule; explicit milestones always apply)")
     p.add_argument("--lr", type=float, default=5e-4)
     p.add_argument("--exp_name", type=str, default="exp_rt1")
     p.add_argument("--log_dir", type=str, default="./exp/logs")
@@ -76,6 +108,15 @@ def build_parser() -> argparse.ArgumentParser:
                         "average under 'ema', eval_rt1.py --ema evaluates it")
     p.add_argument("--no_ema_warmup", action="store_true",
                    help="use --ema_decay from the first step instead of min(decay, (1 + t) / (10 + t))")
+    p.add_argument("--lr_schedule", choices=["none"] + list(LR_SCHEDULES), default="none",
+                   help="per-step learning-rate factor on every group's lr, formed on the device from the effective "
+                        "Adam step (skipped steps do not count): linear warm-up over --warmup_steps, then constant, "
+                        "linear or cosine decay to --min_lr_ratio at --lr_decay_steps, or inverse-sqrt decay")
+    p.add_argument("--warmup_steps", type=int, default=0, help="optimizer steps of linear warm-up (the first uses 1/W)")
+    p.add_argument("--lr_decay_steps", type=int, default=0,
+                   help="optimizer step at which linear / cosine reach --min_lr_ratio (0 = the whole run: max_epochs * "
+                        "ceil(batches per epoch / accumulate_grad_batches))")
+    p.add_argument("--min_lr_ratio", type=float, default=0.0, help="floor of the decay as a fraction of the lr")
     p.add_argument("--bucket_cap_mb", type=float, default=32.0)
     p.add_argument("--no_broadcast_buffers", action="store_true")
     p.add_argument("--comm", choices=["torch", "native"], default="torch",
@@ -218,14 +259,16 @@ def train(args):
     # checks it once against the eager bucketed DP step on the first batch (bitwise, every rank) and falls back to the
     # eager step if they differ (Trainer._check_graph)
     use_graph = args.graph in ("on", "auto")
-    engine = TrainEngine(model, cfg, lr=args.lr, milestones=args.milestones, weight_decay=args.weight_decay,
+    lr_schedule = resolve_lr_schedule(args, train_loader)
+    engine = TrainEngine(model, cfg, lr=args.lr, milestones=resolve_milestones(args), weight_decay=args.weight_decay,
                          bucket_cap_mb=args.bucket_cap_mb, broadcast_buffers=not args.no_broadcast_buffers,
                          comm=args.comm, graph=use_graph,
                          max_grad_norm=args.gradient_clip_val if args.gradient_clip_val > 0 else None,
                          skip_nonfinite=args.skip_nonfinite_steps,
                          accumulate_grad_batches=args.accumulate_grad_batches, ema_decay=args.ema_decay,
                          ema_warmup=not args.no_ema_warmup, no_decay_norm_bias=args.no_decay_norm_bias,
-                         backbone_lr_mult=args.backbone_lr_mult, pretrained=bool(args.pretrained or args.resume))
+                         backbone_lr_mult=args.backbone_lr_mult, pretrained=bool(args.pretrained or args.resume),
+                         lr_schedule=lr_schedule)
     if ctx.is_main:
         print(f"[train] gradient_clip_val {args.gradient_clip_val if args.gradient_clip_val > 0 else 'off'}, "
               f"skip_nonfinite_steps {'on' if args.skip_nonfinite_steps else 'off'}, "
@@ -234,6 +277,8 @@ def train(args):
             print("[train] parameter groups: " + ", ".join(
                 f"{g.get('name')} ({len(g['params'])} tensors, lr {g['lr']:.3g}, weight_decay {g['weight_decay']:g})"
                 for g in engine.optimizer.param_groups), flush=True)
+        if lr_schedule is not None:
+            print(f"[train] lr_schedule {lr_schedule}, milestones {resolve_milestones(args)}", flush=True)
         if args.ema_decay > 0:
             print(f"[train] ema_decay {args.ema_decay} (warm-up {'off' if args.no_ema_warmup else 'on'})", flush=True)
     ckpt = ModelCheckpoint(os.path.join(args.ckpt_dir, args.exp_name), every_n_epochs=args.ckpt_every_n_epochs)
@@ -300,6 +345,17 @@ def check_args(parser, args):
     if args.backbone_lr_mult != 1.0 and not (args.pretrained or args.resume):
         parser.error("--backbone_lr_mult needs --pretrained or --resume: a randomly initialised backbone has no "
                      "pretrained weights to protect with a smaller learning rate")
+    if args.warmup_steps < 0:
+        parser.error(f"--warmup_steps must be >= 0, got {args.warmup_steps}")
+    if args.lr_decay_steps < 0:
+        parser.error(f"--lr_decay_steps must be >= 0 (0 = the whole run), got {args.lr_decay_steps}")
+    if not 0.0 <= args.min_lr_ratio <= 1.0:
+        parser.error(f"--min_lr_ratio must be in [0, 1], got {args.min_lr_ratio}")
+    if args.lr_schedule in ("linear", "cosine") and 0 < args.lr_decay_steps <= args.warmup_steps:
+        parser.error(f"--lr_decay_steps ({args.lr_decay_steps}) must be greater than --warmup_steps "
+                     f"({args.warmup_steps}) for --lr_schedule {args.lr_schedule}")
+    if args.lr_schedule == "none" and (args.warmup_steps or args.lr_decay_steps or args.min_lr_ratio):
+        parser.error("--warmup_steps / --lr_decay_steps / --min_lr_ratio need --lr_schedule")
 
 
 def main(argv=None):

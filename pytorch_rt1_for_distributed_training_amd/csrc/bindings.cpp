@@ -271,6 +271,53 @@ void flat_adam_groups_dev(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v
                  W);
 }
 
+// per-step learning-rate schedule formed on the device (lr_schedule_kernel): state[1] and, when given, group_state[g][0]
+// <- lr_base[g] * f(t); sched_state fp32[4] <- {f, t, 0, 0}.  kind 0..3 = constant, linear, cosine, rsqrt.
+void lr_schedule_dev(at::Tensor state, at::Tensor lr_base, at::Tensor sched_state, const OptT& group_state,
+                     const OptT& clip_state, int64_t kind, int64_t warmup_steps, int64_t decay_steps,
+                     double min_lr_ratio) {
+    const char* W = "lr_schedule_dev";
+    check_dev(state, "state", at::kFloat);
+    check_dev(lr_base, "lr_base", at::kFloat);
+    check_dev(sched_state, "sched_state", at::kFloat);
+    TORCH_CHECK(kind >= 0 && kind <= 3, W, ": kind is ", kind, ", expected 0 (constant), 1 (linear), 2 (cosine) or 3 "
+                "(rsqrt)");
+    TORCH_CHECK(warmup_steps >= 0, W, ": warmup_steps is ", warmup_steps, ", expected >= 0");
+    TORCH_CHECK((kind != 1 && kind != 2) || decay_steps > warmup_steps, W, ": decay_steps is ", decay_steps,
+                ", expected > warmup_steps (", warmup_steps, ") for the linear and cosine schedules");
+    TORCH_CHECK(min_lr_ratio >= 0.0 && min_lr_ratio <= 1.0, W, ": min_lr_ratio is ", min_lr_ratio,
+                ", expected a value in [0, 1]");
+    const int64_t G = lr_base.numel();
+    TORCH_CHECK(G >= 1 && G <= 16, W, ": lr_base has ", G, " entries, expected one per group for 1 to 16 groups");
+    TORCH_CHECK(state.numel() >= 2, W, ": state has ", state.numel(), " entries, expected {step, lr}");
+    TORCH_CHECK(sched_state.numel() >= 4 && aligned16(sched_state), W,
+                ": sched_state must be fp32[4], 16-byte aligned");
+    TORCH_CHECK(lr_base.device() == state.device(), W, ": lr_base on another device");
+    TORCH_CHECK(sched_state.device() == state.device(), W, ": sched_state on another device");
+    TORCH_CHECK(!overlaps(sched_state, state) && !overlaps(sched_state, lr_base) && !overlaps(lr_base, state), W,
+                ": state, lr_base and sched_state must not alias one another");
+    float* gs = nullptr;
+    if (group_state.has_value() && group_state->defined()) {
+        check_dev(*group_state, "group_state", at::kFloat);
+        TORCH_CHECK(group_state->numel() == 4 * G, W, ": group_state has ", group_state->numel(),
+                    " entries, expected 4 per group for the ", G, " groups of lr_base");
+        TORCH_CHECK(group_state->device() == state.device(), W, ": group_state on another device");
+        TORCH_CHECK(!overlaps(*group_state, state) && !overlaps(*group_state, lr_base) &&
+                    !overlaps(*group_state, sched_state), W, ": group_state must not alias another argument");
+        gs = group_state->data_ptr<float>();
+    }
+    const float* cs = nullptr;
+    if (clip_state.has_value() && clip_state->defined()) {
+        check_clip_state(*clip_state, W);
+        TORCH_CHECK(clip_state->device() == state.device(), W, ": clip_state on another device");
+        cs = clip_state->data_ptr<float>();
+    }
+    check_launch(rt1_lr_schedule_dev(state.data_ptr<float>(), cs, lr_base.data_ptr<float>(), gs,
+                                     sched_state.data_ptr<float>(), (int)G, (int)kind, warmup_steps, decay_steps,
+                                     min_lr_ratio, cur_stream()),
+                 W);
+}
+
 // Deterministic fixed-order sum over the rows of B x [R, C] (fp32 or bf16, contiguous) -> B x [C] fp32
 // (csrc/kernels/reduce.hip).  Replaces ATen's tall-reduction path, whose cross-workgroup semaphore combine gave
 // wrong weight gradients under hipGraph replay.
@@ -1603,6 +1650,8 @@ PYBIND11_MODULE(_rt1_hip, m) {
     m.def("flat_adam_ema_dev", &flat_adam_ema_dev, "flat_adam_dev / flat_adam_clip_dev that also updates the EMA of the weights");
     m.def("flat_adam_groups_dev", &flat_adam_groups_dev,
           "the device-state Adam forms (plain, clip, EMA, both) with lr / weight_decay per parameter group");
+    m.def("lr_schedule_dev", &lr_schedule_dev,
+          "per-step lr schedule on the device: state[1] / group_state[g][0] <- lr_base[g] * f(effective Adam step)");
     m.def("gradnorm_partials", &gradnorm_partials, "fp64 partial sums grad_sumsq writes for n floats");
     m.def("grad_sumsq", &grad_sumsq, "deterministic sum of squares of a flat fp32 gradient -> fp64 partials");
     m.def("grad_clip_finalize", &grad_clip_finalize, "partials -> clip_state {norm, coef, ok, counters}");

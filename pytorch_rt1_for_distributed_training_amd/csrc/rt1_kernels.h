@@ -32,6 +32,13 @@ int rt1_flat_adam_groups_dev(float* p, const float* g, float* m, float* v, float
                              const float* group_state, const uint8_t* chunk_group, int G, const float* clip_state,
                              float* ema_state, float beta1, float beta2, float eps, float grad_scale,
                              float one_minus_decay, int warmup, hipStream_t stream);
+// lr_schedule.hip: the per-step schedule factor f(t) of the effective Adam step t = state[0] - skipped steps, formed in
+// fp64 and rounded once: state[1] <- lr_base[0] * f, group_state[g][0] <- lr_base[g] * f (group_state may be nullptr),
+// sched_state fp32[4] <- {f, t, 0, 0}; nothing is written on a skipped step.  kind 0..3 = constant, linear, cosine,
+// rsqrt; warmup >= 0; decay > warmup for linear / cosine; 0 <= min_ratio <= 1; 1 <= G <= 16.  Run before the Adam launch.
+int rt1_lr_schedule_dev(float* state, const float* clip_state, const float* lr_base, float* group_state,
+                        float* sched_state, int G, int kind, int64_t warmup, int64_t decay, double min_ratio,
+                        hipStream_t stream);
 
 // gradnorm.hip (deterministic global gradient norm -> clip_state fp32[8] = {norm, coef, ok, skipped steps, clipped
 // steps, consecutive skipped steps, 0, 0}; rt1_gradnorm_partials: workgroups / fp64 partials for n floats, a function

@@ -25,10 +25,18 @@ group by group; a capture with more than one group always records the grouped
 kernel, so a later scheduler step cannot invalidate the graph.
 ``build_param_groups`` makes the usual groups from a model: no weight decay on
 norms, biases and embeddings, a smaller learning rate on the pretrained backbone.
+
+Per-step schedule (``lr_schedule=dict(kind, warmup_steps, decay_steps, min_lr_ratio)``, off by default): linear warm-up,
+then constant / linear / cosine / inverse-sqrt decay, as one factor ``lr_factor(t)`` on every group's base lr.  Nothing
+per step comes from the host: one tiny launch in front of the Adam launch (``ops.adam.lr_schedule_dev``) forms the
+factor on the device from the effective Adam step ``t`` -- the ``t`` of the bias corrections and of the EMA warm-up,
+which does not count skipped steps -- and writes ``base_g * f`` where the Adam kernels read their lr.  ``param_groups``
+keep the base learning rates, so ``MultiStepLR`` composes with it.
 """
 from __future__ import annotations
 
 import math
+import warnings
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
@@ -37,6 +45,62 @@ from ..parallel.flat import ALIGN, FlatParameters
 
 MAX_GROUPS = 16          # ops.adam.MAX_GROUPS: group_state is at most [16, 4]
 DEFAULT_GROUP = "all"    # how an unnamed group (the single default one) is called in lrs / layouts
+LR_SCHEDULE_KINDS = ("constant", "linear", "cosine", "rsqrt")    # ops.adam.SCHED_KINDS, in the kernel's order
+
+
+def lr_factor(kind: str, t, warmup, decay, min_ratio) -> float:
+    """The per-step schedule factor of the effective Adam step ``t >= 1`` (skipped steps do not count), in fp64 -- the
+    formula ``csrc/kernels/lr_schedule.hip`` evaluates on the device, operation by operation.  With ``W = warmup``,
+    ``N = decay``, ``r = min_ratio``: ``t / W`` while ``t <= W`` (``W > 0``), then with
+    ``q = min(1, (t - W) / (N - W))``
+
+    * ``constant``: 1;
+    * ``linear``: ``1 - (1 - r) q``;
+    * ``cosine``: ``r + (1 - r) (1 + cos(pi q)) / 2``;
+    * ``rsqrt``: ``max(r, sqrt(max(W, 1) / t))`` (``N`` unused).
+
+    At ``q = 1`` the decaying kinds return ``r`` itself, not a rounding of it."""
+    if kind not in LR_SCHEDULE_KINDS:
+        raise ValueError(f"lr schedule kind must be one of {LR_SCHEDULE_KINDS}, got {kind!r}")
+    t, W, N, r = float(t), float(warmup), float(decay), float(min_ratio)
+    if not t >= 1.0:
+        raise ValueError(f"the Adam step t must be >= 1, got {t!r}")
+    if W > 0.0 and t <= W:
+        return t / W
+    if kind == "constant":
+        return 1.0
+    if kind == "rsqrt":
+        return max(r, math.sqrt(max(W, 1.0) / t))
+    q = (t - W) / (N - W)
+    if q >= 1.0:
+        return r
+    if kind == "linear":
+        return 1.0 - (1.0 - r) * q
+    return r + (1.0 - r) * (1.0 + math.cos(math.pi * q)) * 0.5
+
+
+def checked_lr_schedule(schedule: Optional[dict]) -> Optional[dict]:
+    """``None`` (or kind ``"none"``): no schedule.  Otherwise the schedule as a dict of Python scalars
+    ``{kind, warmup_steps, decay_steps, min_lr_ratio}`` after the refusals the kernel binding makes too."""
+    if schedule is None or schedule.get("kind") in (None, "none"):
+        return None
+    extra = set(schedule) - {"kind", "warmup_steps", "decay_steps", "min_lr_ratio"}
+    if extra:
+        raise ValueError(f"lr_schedule has unknown keys {sorted(extra)}")
+    kind = schedule["kind"]
+    W, N, r = schedule.get("warmup_steps", 0), schedule.get("decay_steps", 0), schedule.get("min_lr_ratio", 0.0)
+    if kind not in LR_SCHEDULE_KINDS:
+        raise ValueError(f"lr_schedule kind must be one of {LR_SCHEDULE_KINDS} (or None), got {kind!r}")
+    for name, v in (("warmup_steps", W), ("decay_steps", N)):
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError(f"lr_schedule {name} must be an integer, got {v!r}")
+    if W < 0:
+        raise ValueError(f"lr_schedule warmup_steps must be >= 0, got {W!r}")
+    if kind in ("linear", "cosine") and not N > W:
+        raise ValueError(f"lr_schedule decay_steps must be > warmup_steps ({W}) for the {kind} schedule, got {N!r}")
+    if not 0.0 <= float(r) <= 1.0:
+        raise ValueError(f"lr_schedule min_lr_ratio must be in [0, 1], got {r!r}")
+    return dict(kind=kind, warmup_steps=int(W), decay_steps=int(N), min_lr_ratio=float(r))
 
 
 class FlatAdam(torch.optim.Optimizer):
@@ -44,7 +108,9 @@ class FlatAdam(torch.optim.Optimizer):
                  weight_decay: float = 0.0, all_params: Optional[Sequence[torch.nn.Parameter]] = None,
                  use_kernel: Optional[bool] = None, max_grad_norm: Optional[float] = None,
                  skip_nonfinite: bool = False, ema_decay: float = 0.0, ema_warmup: bool = True,
-                 param_names: Optional[Dict[int, str]] = None, groups: Optional[Sequence[dict]] = None):
+                 param_names: Optional[Dict[int, str]] = None, groups: Optional[Sequence[dict]] = None,
+                 lr_schedule: Optional[dict] = None):
+        lr_schedule = checked_lr_schedule(lr_schedule)
         if not 0.0 <= float(ema_decay) < 1.0:
             raise ValueError(f"ema_decay must be in [0, 1) (0 = off), got {ema_decay!r}")
         self.flat = flat
@@ -108,6 +174,16 @@ class FlatAdam(torch.optim.Optimizer):
         if self.ema_enabled:
             self.ema = flat.data.detach().clone()
             self.ema_state = torch.zeros(4, dtype=torch.float32, device=flat.data.device)
+        # per-step learning-rate schedule (off at None: no tensor, no launch), a run constant.  The groups' lr in
+        # param_groups stay the BASE learning rates (what MultiStepLR scales per epoch); one launch per step
+        # (ops.adam.lr_schedule_dev, before the Adam launch) writes base * f(t) into dev_state[1] / group_state[:, 0],
+        # with t the effective Adam step as the device knows it.  lr_base is fp32[G], the device copy of the base
+        # learning rates; sched_state is fp32[4] = {f of the last applied update, its t, 0, 0}
+        self.lr_schedule = lr_schedule
+        self.lr_base = self.sched_state = None
+        if lr_schedule is not None:
+            self.lr_base = torch.zeros(len(self.param_groups), dtype=torch.float32, device=flat.data.device)
+            self.sched_state = torch.zeros(4, dtype=torch.float32, device=flat.data.device)
 
     @torch.no_grad()
     def step(self, closure=None, grad_scale: float = 1.0):
@@ -133,6 +209,11 @@ class FlatAdam(torch.optim.Optimizer):
                 self._kernel.grad_norm_clip_(self.flat.grad, self.clip_state, self._partials,
                                              max_norm=self.max_grad_norm, grad_scale=grad_scale,
                                              skip_nonfinite=self.skip_nonfinite)
+            if self.lr_schedule is not None:
+                # this step's lr of every group, from the device's own t: the Adam launch below reads what this writes
+                self._kernel.lr_schedule_dev(self.dev_state, self.lr_base, self.sched_state,
+                                             group_state=self.group_state, clip_state=self.clip_state,
+                                             **self.lr_schedule)
             if grouped:
                 self._kernel.flat_adam_groups_dev_step(self.flat.data, self.flat.grad, self.exp_avg, self.exp_avg_sq,
                                                        self.dev_state, self.group_state, self.chunk_group,
@@ -169,8 +250,15 @@ class FlatAdam(torch.optim.Optimizer):
                 grad = grad * coef
             t -= self.skipped_steps
         p = self.flat.data
+        f = None
+        if self.lr_schedule is not None:
+            # the kernel's work on the host: the factor in fp64 rounded once, fp32 products with the base lrs
+            f = self._apply_schedule_host(t)
+            lr = float(torch.tensor(lr, dtype=torch.float32) * f)
         if grouped:
             lr_e, wd_e = self._per_element()         # the same update with lr and wd expanded per element
+            if f is not None:
+                lr_e = lr_e * f
             p.mul_(1.0 - lr_e * wd_e)
         elif wd:
             p.mul_(1.0 - lr * wd)
@@ -216,6 +304,44 @@ class FlatAdam(torch.optim.Optimizer):
     @property
     def clipped_steps(self) -> int:
         return int(self.clip_state[4]) if self.clip_state is not None else 0
+
+    # -------------------------------------------------------------- per-step learning-rate schedule
+    def _apply_schedule_host(self, t: int) -> torch.Tensor:
+        """What ``lr_schedule_dev`` writes for the effective Adam step ``t``, from the host (the CPU / no-kernel path,
+        and a loaded checkpoint); returns the fp32 factor (a 0-d host tensor)."""
+        f = torch.tensor(lr_factor(t=t, **self._factor_args()), dtype=torch.float32)
+        base = torch.tensor([x[0] for x in self.host_groups()], dtype=torch.float32)
+        scaled = (base * f).to(self.dev_state.device)
+        self.lr_base.copy_(base)
+        self.dev_state[1] = scaled[0]
+        if self.group_state is not None:
+            self.group_state[:, 0] = scaled
+        self.sched_state.copy_(torch.stack([f, torch.tensor(float(t)), torch.zeros(()), torch.zeros(())]))
+        return f
+
+    def _factor_args(self) -> dict:
+        s = self.lr_schedule
+        return dict(kind=s["kind"], warmup=s["warmup_steps"], decay=s["decay_steps"], min_ratio=s["min_lr_ratio"])
+
+    @property
+    def current_lr(self) -> torch.Tensor:
+        """The first group's learning rate as the Adam launch reads it (``dev_state[1]``): a 0-d device view, no sync.
+        With a schedule it is base lr times the factor of the last applied update."""
+        if self.lr_schedule is None and self._kernel is None:
+            return torch.tensor(self.param_groups[0]["lr"], dtype=torch.float32)     # no device copy is kept here
+        return self.dev_state[1]
+
+    @property
+    def current_lrs(self) -> Dict[str, torch.Tensor]:
+        """``current_lr`` of every group by name (views of ``group_state[:, 0]`` with several groups)."""
+        if self.group_state is None or (self.lr_schedule is None and self._kernel is None):
+            return {self.group_names[0]: self.current_lr}
+        return {n: self.group_state[gi, 0] for gi, n in enumerate(self.group_names)}
+
+    @property
+    def lr_factor_now(self) -> Optional[torch.Tensor]:
+        """The schedule factor of the last applied update (``sched_state[0]``): a 0-d device view, no sync."""
+        return self.sched_state[0] if self.sched_state is not None else None
 
     # -------------------------------------------------------------- exponential moving average of the weights
     @property
@@ -335,8 +461,19 @@ class FlatAdam(torch.optim.Optimizer):
 
     def write_device_state(self, step: int):
         """Host -> device write of {step, group 0's lr} and, with several groups, of every group's {lr, wd, 0, 0}
-        (small H2D copies; outside any capture)."""
+        (small H2D copies; outside any capture).  Under a schedule: of the step, the base lrs and every group's wd."""
         hg = self.host_groups()
+        if self.lr_base is not None:
+            # under a schedule the lr slots (dev_state[1], group_state[:, 0]) belong to the schedule op, which forms them
+            # from lr_base before every Adam launch: the host writes the base learning rates there and leaves the
+            # slots alone, so current_lr stays the lr of the last applied update
+            self.lr_base.copy_(torch.tensor([x[0] for x in hg], dtype=torch.float32))
+            self.dev_state[0:1].copy_(torch.tensor([float(step)]))
+            if self.group_state is not None:
+                self.group_state[:, 1:].copy_(torch.tensor([[x[1], 0.0, 0.0] for x in hg], dtype=torch.float32))
+            self._dev_step = int(step)
+            self._dev_groups = hg
+            return
         self.dev_state.copy_(torch.tensor([float(step), hg[0][0]]))
         if self.group_state is not None:
             self.group_state.copy_(torch.tensor([[x[0], x[1], 0.0, 0.0] for x in hg], dtype=torch.float32))
@@ -370,10 +507,17 @@ class FlatAdam(torch.optim.Optimizer):
                 state[index[id(p)]] = {"step": torch.tensor(float(step)),
                                        "exp_avg": self.exp_avg[o:o + n].view_as(p).detach().clone(),
                                        "exp_avg_sq": self.exp_avg_sq[o:o + n].view_as(p).detach().clone()}
-        return {"state": state, "param_groups": groups}
+        out = {"state": state, "param_groups": groups}
+        if self.lr_schedule is not None:
+            out["lr_schedule"] = dict(self.lr_schedule)      # its position is the effective step above
+        return out
 
     def load_state_dict(self, sd: Dict):
         groups = sd["param_groups"]
+        if "lr_schedule" in sd and checked_lr_schedule(sd["lr_schedule"]) != self.lr_schedule:
+            # extending or reshaping a run is legitimate: the running optimizer's schedule holds
+            warnings.warn(f"the loaded state was written under the lr schedule {sd['lr_schedule']}, this optimizer "
+                          f"runs {self.lr_schedule}: continuing with the latter from the restored step")
         # torch's own refusals, with both layouts named: a checkpoint's groups must be this optimizer's
         if len(groups) != len(self.param_groups):
             raise ValueError(f"loaded state dict has a different number of parameter groups: it holds "
@@ -404,6 +548,12 @@ class FlatAdam(torch.optim.Optimizer):
         if self.clip_state is not None:
             self.clip_state.zero_()      # the host counter is the effective step again
             self._dev_step = None
+        if self.sched_state is not None:
+            # {f, t} as the restored step's update left them under this schedule (the next one rewrites both)
+            if self.step_count > 0:
+                self._apply_schedule_host(self.step_count)
+            else:
+                self.sched_state.zero_()
 
 
 def backbone_parameters(model: torch.nn.Module) -> List[torch.nn.Parameter]:

@@ -53,6 +53,13 @@ learning rate on the pretrained backbone) and the Adam launch looks the group up
 captured graph stays valid.  ``backbone_lr_mult != 1`` asks for pretrained weights (``pretrained``, else the model's
 ``backbone_pretrained`` mark that ``models.load_pretrained_backbone`` leaves).  ``lrs`` gives every group's lr by name.
 
+``lr_schedule=dict(kind, warmup_steps, decay_steps, min_lr_ratio)`` (None = off, and then nothing here changes): a
+per-step factor on every group's base lr -- linear warm-up, then constant / linear / cosine / inverse-sqrt decay
+(``engine.optim.lr_factor``) -- formed on the device by one tiny launch inside ``optimizer.step()``
+(``ops.adam.lr_schedule_dev``), from the effective Adam step the bias corrections use, so every step path above carries
+it, a skipped step does not advance it and no step waits for a host write.  ``lr`` / ``lrs`` stay the base learning
+rates that ``MultiStepLR`` scales per epoch; ``lr_now`` / ``lrs_now`` read the scheduled values back from the device.
+
 No ``network_state`` is fabricated (the reference samples a random one on the
 CPU and copies it to the GPU every step only to read its shape).
 """
@@ -141,7 +148,7 @@ class TrainEngine:
                  graph: bool = False, max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False,
                  accumulate_grad_batches: int = 1, ema_decay: float = 0.0, ema_warmup: bool = True,
                  no_decay_norm_bias: bool = False, backbone_lr_mult: float = 1.0,
-                 pretrained: Optional[bool] = None):
+                 pretrained: Optional[bool] = None, lr_schedule: Optional[dict] = None):
         if not isinstance(backbone_lr_mult, (int, float)) or not backbone_lr_mult > 0:
             raise ValueError(f"backbone_lr_mult must be a number > 0, got {backbone_lr_mult!r}")
         if pretrained is None:
@@ -197,7 +204,8 @@ class TrainEngine:
         self.optimizer = FlatAdam(self.flat, lr=lr, weight_decay=weight_decay,
                                   all_params=list(self.model.parameters()), max_grad_norm=max_grad_norm,
                                   skip_nonfinite=skip_nonfinite, ema_decay=ema_decay, ema_warmup=ema_warmup,
-                                  param_names={id(p): n for n, p in self.model.named_parameters()}, groups=groups)
+                                  param_names={id(p): n for n, p in self.model.named_parameters()}, groups=groups,
+                                  lr_schedule=lr_schedule)
         # skip_nonfinite: the forward of a bad batch has already written the BN running statistics when the norm
         # kernel notices, so they live in one flat buffer (the data-parallel one when there is one) with a shadow copy
         # of the last good state; buffer_guard_ advances or rolls back right after the optimizer step
@@ -602,7 +610,9 @@ class TrainEngine:
                         grad=(self.flat.grad.clone() if self.accumulate_grad_batches > 1 else None),
                         micro=self.micro_step, stepped=self.stepped,
                         ema=(opt.ema.clone() if opt.ema is not None else None),
-                        ema_state=(opt.ema_state.clone() if opt.ema_state is not None else None))
+                        ema_state=(opt.ema_state.clone() if opt.ema_state is not None else None),
+                        lr_base=(opt.lr_base.clone() if opt.lr_base is not None else None),
+                        sched_state=(opt.sched_state.clone() if opt.sched_state is not None else None))
 
     def _restore(self, s: Dict):
         from ..ops import rng as _rng
@@ -627,6 +637,9 @@ class TrainEngine:
             if s["ema"] is not None:
                 opt.ema.copy_(s["ema"])
                 opt.ema_state.copy_(s["ema_state"])
+            if s["lr_base"] is not None:
+                opt.lr_base.copy_(s["lr_base"])
+                opt.sched_state.copy_(s["sched_state"])
         self.micro_step, self.stepped = s["micro"], s["stepped"]
         opt.step_count, opt._dev_step, opt._dev_groups = s["step"], s["dev_step"], s["dev_groups"]
         if s["rng"] is not None:
@@ -716,3 +729,18 @@ class TrainEngine:
     def lrs(self) -> Dict[str, float]:
         """Learning rate of every parameter group by name (``lr`` is the first group's)."""
         return {n: g["lr"] for n, g in zip(self.optimizer.group_names, self.optimizer.param_groups)}
+
+    @property
+    def lr_now(self) -> float:
+        """The first group's learning rate as the last applied update used it: ``lr`` without a per-step schedule, else
+        the scheduled value read back from the device (a sync: for log points)."""
+        if self.optimizer.lr_schedule is None:
+            return self.lr
+        return float(self.optimizer.current_lr)
+
+    @property
+    def lrs_now(self) -> Dict[str, float]:
+        """``lr_now`` of every parameter group by name."""
+        if self.optimizer.lr_schedule is None:
+            return self.lrs
+        return {n: float(v) for n, v in self.optimizer.current_lrs.items()}

@@ -32,6 +32,10 @@ restored weights when the checkpoint has none).  ``eval_loss`` and the checkpoin
 With more than one parameter group (the engine's ``no_decay_norm_bias`` / ``backbone_lr_mult``) each epoch also logs
 ``lr/<group>``; checkpoints carry the groups in the optimizer and scheduler states, and ``resume`` restores their names
 and learning rates -- into the same group layout only: the resumed run's flags must reproduce it.
+
+With the engine's ``lr_schedule`` the ``log_every_n_steps`` log point also logs ``lr-Adam`` (and ``lr/<group>`` with
+several groups) as the last applied update used them, read back from the device at the point that already synchronises
+for the loss; the per-epoch ``lr-Adam`` stays the base learning rate that ``MultiStepLR`` scales.
 """
 from __future__ import annotations
 
@@ -222,6 +226,7 @@ class Trainer:
             opt = e.optimizer
             clip_on = bool(getattr(opt, "clip_enabled", False))
             skip_on = bool(getattr(opt, "skip_nonfinite", False))
+            sched_on = getattr(opt, "lr_schedule", None) is not None
             # skip_nonfinite: means over the finite-loss steps only (device-side masked sums and counts, no sync)
             tcount = wcount = None
             t0 = time.perf_counter()
@@ -245,12 +250,19 @@ class Trainer:
                     if clip_on:
                         metrics.update(grad_norm=float(opt.last_grad_norm), clipped_steps=opt.clipped_steps,
                                        skipped_steps=opt.skipped_steps)
+                    lr_shown = e.lr
+                    if sched_on:
+                        # the scheduled values of the last applied update, from the device (this point has synchronised)
+                        now = e.lrs_now
+                        lr_shown = metrics["lr-Adam"] = next(iter(now.values()))
+                        if len(now) > 1:
+                            metrics.update({f"lr/{name}": v for name, v in now.items()})
                     self._log(metrics)
                     window, wn, wcount, wsteps = None, 0, None, 0
                     if self.verbose:
                         extra = (f" grad_norm {metrics['grad_norm']:.4g} clipped {metrics['clipped_steps']} "
                                  f"skipped {metrics['skipped_steps']}") if clip_on else ""
-                        print(f"epoch {epoch} step {e.global_step} train_loss {step_loss:.6f} lr {e.lr:.2e}{extra}",
+                        print(f"epoch {epoch} step {e.global_step} train_loss {step_loss:.6f} lr {lr_shown:.2e}{extra}",
                               flush=True)
 
             for batch in self._iter(train_loader, self.limit_train):

@@ -85,6 +85,25 @@ def flat_adam_groups_dev_step(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor,
                                 eps, grad_scale, float(one_minus_decay), bool(warmup))
 
 
+SCHED_KINDS = ("constant", "linear", "cosine", "rsqrt")   # the kernel's kind argument is the index
+SCHED_STATE_SLOTS = 4  # {factor of the last applied update, its Adam step t, 0, 0}
+
+
+def lr_schedule_dev(state: torch.Tensor, lr_base: torch.Tensor, sched_state: torch.Tensor, *,
+                    group_state: torch.Tensor = None, clip_state: torch.Tensor = None, kind: str, warmup_steps: int,
+                    decay_steps: int = 0, min_lr_ratio: float = 0.0):
+    """The per-step learning-rate schedule, formed on the device (``csrc/kernels/lr_schedule.hip``, one wave, run
+    before the Adam op of the step): with ``t = state[0]`` (minus the skipped steps of ``clip_state``) and
+    ``f = engine.optim.lr_factor(kind, t, warmup_steps, decay_steps, min_lr_ratio)`` evaluated in fp64 and rounded once
+    to fp32, ``state[1] <- lr_base[0] * f``, ``group_state[g, 0] <- lr_base[g] * f`` (when given; fp32 ``[G, 4]`` for
+    the ``G <= 16`` entries of ``lr_base``) and ``sched_state`` fp32[4] ``<- {f, t, 0, 0}``.  A skipped step
+    (``clip_state[2] == 0``) writes nothing."""
+    if kind not in SCHED_KINDS:
+        raise ValueError(f"lr_schedule_dev: kind is {kind!r}, expected one of {SCHED_KINDS}")
+    load().lr_schedule_dev(state, lr_base, sched_state, group_state, clip_state, SCHED_KINDS.index(kind),
+                           int(warmup_steps), int(decay_steps), float(min_lr_ratio))
+
+
 def reference_adam_groups_step(p, g, m, v, chunk_group, group_lr, group_wd, *, beta1, beta2, eps, step,
                                grad_scale=1.0):
     """Plain PyTorch oracle of the grouped update in the dtype of its operands (fp64 for a referee): the math of
