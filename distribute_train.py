@@ -117,6 +117,14 @@ def build_parser() -> argparse.ArgumentParser:
                    help="optimizer step at which linear / cosine reach --min_lr_ratio (0 = the whole run: max_epochs * "
                         "ceil(batches per epoch / accumulate_grad_batches))")
     p.add_argument("--min_lr_ratio", type=float, default=0.0, help="floor of the decay as a fraction of the lr")
+    p.add_argument("--label_smoothing", type=float, default=0.0,
+                   help="training objective: label smoothing in [0, 1) over all vocab bins (torch's cross_entropy "
+                        "convention); validation and test stay the plain cross-entropy; train_nll_step is logged")
+    p.add_argument("--z_loss", type=float, default=0.0,
+                   help="training objective: + z_loss * logsumexp(logits)^2 per action token (PaLM's auxiliary loss; "
+                        "1e-4 is usual); validation and test stay the plain cross-entropy")
+    p.add_argument("--token_accuracy", action="store_true",
+                   help="log the action-token accuracy: train_acc_step, eval_acc, test_acc and per-slot .../tok<a>")
     p.add_argument("--bucket_cap_mb", type=float, default=32.0)
     p.add_argument("--no_broadcast_buffers", action="store_true")
     p.add_argument("--comm", choices=["torch", "native"], default="torch",
@@ -268,7 +276,8 @@ def train(args):
                          accumulate_grad_batches=args.accumulate_grad_batches, ema_decay=args.ema_decay,
                          ema_warmup=not args.no_ema_warmup, no_decay_norm_bias=args.no_decay_norm_bias,
                          backbone_lr_mult=args.backbone_lr_mult, pretrained=bool(args.pretrained or args.resume),
-                         lr_schedule=lr_schedule)
+                         lr_schedule=lr_schedule, label_smoothing=args.label_smoothing, z_loss=args.z_loss,
+                         token_accuracy=args.token_accuracy)
     if ctx.is_main:
         print(f"[train] gradient_clip_val {args.gradient_clip_val if args.gradient_clip_val > 0 else 'off'}, "
               f"skip_nonfinite_steps {'on' if args.skip_nonfinite_steps else 'off'}, "
@@ -281,6 +290,10 @@ def train(args):
             print(f"[train] lr_schedule {lr_schedule}, milestones {resolve_milestones(args)}", flush=True)
         if args.ema_decay > 0:
             print(f"[train] ema_decay {args.ema_decay} (warm-up {'off' if args.no_ema_warmup else 'on'})", flush=True)
+        if args.label_smoothing or args.z_loss or args.token_accuracy:
+            print(f"[train] label_smoothing {args.label_smoothing:g}, z_loss {args.z_loss:g} (training mode only: "
+                  f"eval_loss / test_loss stay the plain CE), token_accuracy {'on' if args.token_accuracy else 'off'}",
+                  flush=True)
     ckpt = ModelCheckpoint(os.path.join(args.ckpt_dir, args.exp_name), every_n_epochs=args.ckpt_every_n_epochs)
     loggers = []
     if ctx.is_main:
@@ -345,6 +358,10 @@ def check_args(parser, args):
     if args.backbone_lr_mult != 1.0 and not (args.pretrained or args.resume):
         parser.error("--backbone_lr_mult needs --pretrained or --resume: a randomly initialised backbone has no "
                      "pretrained weights to protect with a smaller learning rate")
+    if not 0.0 <= args.label_smoothing < 1.0:                # NaN fails both comparisons
+        parser.error(f"--label_smoothing must be in [0, 1), got {args.label_smoothing}")
+    if not 0.0 <= args.z_loss < float("inf"):
+        parser.error(f"--z_loss must be finite and >= 0, got {args.z_loss}")
     if args.warmup_steps < 0:
         parser.error(f"--warmup_steps must be >= 0, got {args.warmup_steps}")
     if args.lr_decay_steps < 0:

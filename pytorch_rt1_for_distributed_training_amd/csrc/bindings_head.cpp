@@ -1,6 +1,7 @@
 // Python bindings for the fused action head (csrc/kernels/head.hip) and the streamed long-history
 // attention backward (csrc/kernels/attention.hip, rt1_attn_bwd_long).  Same rules as bindings.cpp: every
 // shape / dtype / device is validated on the host before a launch, launches go to torch's current stream.
+#include <cmath>
 #include <cstdlib>
 
 #include <torch/extension.h>
@@ -54,9 +55,12 @@ const uint32_t* seed_ptr(const OptT& t) {
 
 bool head_ce_supported(int64_t V, int64_t E) { return rt1_head_ce_supported((int)V, (int)E) != 0; }
 
-// hidden [B, S, 512] fp32, pos [P] int32 (values in [0, S), clamped in-kernel), W [V, 512] bf16, bias [V] fp32,
-// target [B*P] int32  ->  ce [R] fp32, pred [R] int32, G [R, V] bf16, hb [R, 512] bf16   (R = B*P)
-std::vector<at::Tensor> head_ce_fwd(at::Tensor hidden, at::Tensor pos, at::Tensor W, at::Tensor bias, at::Tensor target) {
+// the head's operands, validated: hidden [B, S, 512] fp32, pos [P] int32 (values in [0, S), clamped in-kernel),
+// W [V, 512] bf16, bias [V] fp32, target [B*P] int32
+struct HeadDims { int64_t S, E, V, P, R; };
+
+HeadDims head_dims(const at::Tensor& hidden, const at::Tensor& pos, const at::Tensor& W, const at::Tensor& bias,
+                   const at::Tensor& target) {
     check_dev(hidden, "hidden", at::kFloat);
     check_dev(pos, "pos", at::kInt);
     check_dev(W, "W", at::kBFloat16);
@@ -72,14 +76,55 @@ std::vector<at::Tensor> head_ce_fwd(at::Tensor hidden, at::Tensor pos, at::Tenso
     const int64_t P = pos.numel(), R = B * P;
     TORCH_CHECK(target.numel() == R, "target must have B*P elements");
     TORCH_CHECK(R > 0 && R < (int64_t)1 << 30, "bad row count");
-    auto ce = at::empty({R}, hidden.options());
-    auto pred = at::empty({R}, pos.options());
-    auto G = at::empty({R, V}, W.options());
-    auto hb = at::empty({R, E}, W.options());
+    return {S, E, V, P, R};
+}
+
+// ->  ce [R] fp32, pred [R] int32, G [R, V] bf16, hb [R, 512] bf16   (R = B*P)
+std::vector<at::Tensor> head_ce_fwd(at::Tensor hidden, at::Tensor pos, at::Tensor W, at::Tensor bias, at::Tensor target) {
+    const HeadDims d = head_dims(hidden, pos, W, bias, target);
+    auto ce = at::empty({d.R}, hidden.options());
+    auto pred = at::empty({d.R}, pos.options());
+    auto G = at::empty({d.R, d.V}, W.options());
+    auto hb = at::empty({d.R, d.E}, W.options());
     check_launch(rt1_head_ce_fwd(hidden.data_ptr<float>(), pos.data_ptr<int>(), bp(W), bias.data_ptr<float>(),
-                                 target.data_ptr<int>(), (int)R, (int)P, (int)S, (int)V, ce.data_ptr<float>(),
+                                 target.data_ptr<int>(), (int)d.R, (int)d.P, (int)d.S, (int)d.V, ce.data_ptr<float>(),
                                  pred.data_ptr<int>(), bp(G), bp(hb), cur_stream()), "head_ce_fwd");
     return {ce, pred, G, hb};
+}
+
+// the regularised objective (label smoothing in [0, 1), z-loss >= 0, finite): -> loss [R] fp32 and, as head_ce_fwd,
+// the plain ce [R], pred [R], G [R, V] (now d loss / d logits), hb [R, 512]
+std::vector<at::Tensor> head_ce_loss_fwd(at::Tensor hidden, at::Tensor pos, at::Tensor W, at::Tensor bias,
+                                         at::Tensor target, double label_smoothing, double z_loss) {
+    TORCH_CHECK(label_smoothing >= 0.0 && label_smoothing < 1.0, "head_ce_loss_fwd: label_smoothing must be in [0, 1), "
+                "got ", label_smoothing);
+    TORCH_CHECK(z_loss >= 0.0 && std::isfinite(z_loss), "head_ce_loss_fwd: z_loss must be finite and >= 0, got ", z_loss);
+    const float eps = (float)label_smoothing, zeta = (float)z_loss;
+    TORCH_CHECK(eps < 1.f && std::isfinite(zeta), "head_ce_loss_fwd: label_smoothing / z_loss out of the fp32 range");
+    const HeadDims d = head_dims(hidden, pos, W, bias, target);
+    auto loss = at::empty({d.R}, hidden.options());
+    auto ce = at::empty({d.R}, hidden.options());
+    auto pred = at::empty({d.R}, pos.options());
+    auto G = at::empty({d.R, d.V}, W.options());
+    auto hb = at::empty({d.R, d.E}, W.options());
+    check_launch(rt1_head_ce_loss_fwd(hidden.data_ptr<float>(), pos.data_ptr<int>(), bp(W), bias.data_ptr<float>(),
+                                      target.data_ptr<int>(), (int)d.R, (int)d.P, (int)d.S, (int)d.V, eps, zeta,
+                                      loss.data_ptr<float>(), ce.data_ptr<float>(), pred.data_ptr<int>(), bp(G), bp(hb),
+                                      cur_stream()), "head_ce_loss_fwd");
+    return {loss, ce, pred, G, hb};
+}
+
+// counters int64 [A, 2] += {rows with pred == target, rows} per action-token slot r % A; pred, target int32 [R]
+void head_token_hits_(at::Tensor pred, at::Tensor target, at::Tensor counters) {
+    check_dev(pred, "pred", at::kInt);
+    check_dev(target, "target", at::kInt);
+    check_dev(counters, "counters", at::kLong);
+    TORCH_CHECK(counters.dim() == 2 && counters.size(1) == 2 && counters.size(0) >= 1 && counters.size(0) <= 32,
+                "counters must be int64 [A, 2], 1 <= A <= 32");
+    const int64_t R = pred.numel(), A = counters.size(0);
+    TORCH_CHECK(target.numel() == R && R > 0 && R < (int64_t)1 << 30, "pred / target must have the same R >= 1 elements");
+    check_launch(rt1_head_token_hits(pred.data_ptr<int>(), target.data_ptr<int>(), (int)R, (int)A,
+                                     counters.data_ptr<int64_t>(), cur_stream()), "head_token_hits_");
 }
 
 // action tokens of the concatenated components in one launch: comps[i] is Box fp32 [..., dims[i]] (dims[i] > 0) or
@@ -389,6 +434,9 @@ void register_head(py::module_& m) {
     m.def("tl_bwd", &tl_bwd);
     m.def("head_ce_supported", &head_ce_supported);
     m.def("head_ce_fwd", &head_ce_fwd);
+    m.def("head_ce_loss_fwd", &head_ce_loss_fwd, py::arg("hidden"), py::arg("pos"), py::arg("W"), py::arg("bias"),
+          py::arg("target"), py::arg("label_smoothing"), py::arg("z_loss"));
+    m.def("head_token_hits_", &head_token_hits_);
     m.def("head_ce_scale", &head_ce_scale);
     m.def("attn_bwd_long", &attn_bwd_long, py::arg("qkv"), py::arg("out"), py::arg("dout"), py::arg("lse"),
           py::arg("L"), py::arg("Kimg"), py::arg("scale"), py::arg("drop_p"), py::arg("seed"),

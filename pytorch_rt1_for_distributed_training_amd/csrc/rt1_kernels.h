@@ -190,6 +190,13 @@ int rt1_action_tokenize(const void* const* comps, const int* kind, const int* di
 int rt1_head_ce_supported(int V, int E);
 int rt1_head_ce_fwd(const float* hidden, const int* pos, const rt1_bf16* W, const float* bias, const int* target,
                     int R, int P, int S, int V, float* ce, int* pred, rt1_bf16* G, rt1_bf16* hb, hipStream_t st);
+// label smoothing eps in [0, 1) and z-loss zeta >= 0 (finite; else hipErrorInvalidValue): loss is the regularised
+// objective, ce the plain one, G = d loss / d logits
+int rt1_head_ce_loss_fwd(const float* hidden, const int* pos, const rt1_bf16* W, const float* bias, const int* target,
+                         int R, int P, int S, int V, float eps, float zeta, float* loss, float* ce, int* pred,
+                         rt1_bf16* G, rt1_bf16* hb, hipStream_t st);
+// counters int64 [A, 2] += {pred == target, rows} per slot r % A (one workgroup, no atomics); 1 <= A <= 32
+int rt1_head_token_hits(const int* pred, const int* target, int R, int A, int64_t* counters, hipStream_t st);
 int rt1_head_ce_scale(const rt1_bf16* G, const float* dce, int R, int V, rt1_bf16* dz, hipStream_t st);
 
 // tokenlearner.hip (one workgroup per frame; P <= 256, C = 512, bottleneck 64, 8 tokens)

@@ -60,6 +60,15 @@ per-step factor on every group's base lr -- linear warm-up, then constant / line
 it, a skipped step does not advance it and no step waits for a host write.  ``lr`` / ``lrs`` stay the base learning
 rates that ``MultiStepLR`` scales per epoch; ``lr_now`` / ``lrs_now`` read the scheduled values back from the device.
 
+``label_smoothing`` / ``z_loss`` / ``token_accuracy`` (0 / 0 / off, and then nothing here changes): the training
+objective becomes ``(1 - eps) nll + eps mean_c(-log p_c) + zeta logsumexp^2`` (``models.policy.token_losses``; on the
+fused head one kernel, ``ops.head``), applied only while the model is in training mode, so ``eval_step`` stays
+the plain CE; ``last_nll`` is then the plain CE of the last training batch (the engine's own copy: a replay clones the
+graph's tensor, and a capture, which records a forward without running it, leaves the eager step's figure in place).
+With ``token_accuracy`` every forward adds {pred == label, rows} per action-token slot to ``token_counters`` (one small
+launch, part of the captured step; every micro-batch of an accumulation window counts); ``read_token_counters`` reads
+and zeroes them.
+
 No ``network_state`` is fabricated (the reference samples a random one on the
 CPU and copies it to the GPU every step only to read its shape).
 """
@@ -148,7 +157,10 @@ class TrainEngine:
                  graph: bool = False, max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False,
                  accumulate_grad_batches: int = 1, ema_decay: float = 0.0, ema_warmup: bool = True,
                  no_decay_norm_bias: bool = False, backbone_lr_mult: float = 1.0,
-                 pretrained: Optional[bool] = None, lr_schedule: Optional[dict] = None):
+                 pretrained: Optional[bool] = None, lr_schedule: Optional[dict] = None,
+                 label_smoothing: float = 0.0, z_loss: float = 0.0, token_accuracy: bool = False):
+        from ..models.policy import checked_objective
+        label_smoothing, z_loss = checked_objective(label_smoothing, z_loss)
         if not isinstance(backbone_lr_mult, (int, float)) or not backbone_lr_mult > 0:
             raise ValueError(f"backbone_lr_mult must be a number > 0, got {backbone_lr_mult!r}")
         if pretrained is None:
@@ -163,6 +175,18 @@ class TrainEngine:
         self.cfg = cfg
         self.device = device or pdist.default_device()
         self.model = model.to(self.device)
+        # training objective and token accuracy (models/policy.py): plain attributes of the model; the {hits, rows}
+        # counters per action-token slot are this engine's device state, not a buffer of the model, so neither the
+        # checkpoint nor the data-parallel buffer broadcast sees them
+        self.model.label_smoothing, self.model.z_loss = label_smoothing, z_loss
+        self.regularised = label_smoothing != 0.0 or z_loss != 0.0
+        self.token_accuracy = bool(token_accuracy)
+        self.token_counters = None
+        if self.token_accuracy:
+            self.token_counters = torch.zeros(self.model._tokens_per_action, 2, dtype=torch.int64, device=self.device)
+        self.model.track_token_accuracy = self.token_accuracy
+        self.model.token_counters = self.token_counters
+        self.last_nll = None       # mean plain CE of the last train_step's batch (regularised objective only)
         self.compute_dtype = torch.bfloat16 if (cfg.dtype == "bf16" and self.device.type == "cuda") else torch.float32
         self.backend = self._select_backend(cfg)
         if self.backend == "hip":
@@ -176,6 +200,8 @@ class TrainEngine:
             order = self._gradient_order(trainable)
         else:
             order = list(reversed(trainable))
+        if self.token_counters is not None:
+            self.token_counters.zero_()            # the order probe's forward counted its synthetic rows
         self.flat = FlatParameters(order, device=self.device)
         # weight-gradient split-K sums folded into the flat gather (parallel/flat.py deferred_sums): one backward per
         # step into an fp32 gradient buffer on the GPU
@@ -231,6 +257,7 @@ class TrainEngine:
         self._segments = None      # SegmentedCapture of the data-parallel graph step
         self._static_batch = None
         self._static_loss = None
+        self._static_nll = None    # forward_loss's last_nll as the captured step wrote it
         # graph-DP comm timing (bench.py): (event before the final waits, event after) per replayed step
         self.comm_timing = None
         self.comm_host_wait_s = 0.0
@@ -291,6 +318,8 @@ class TrainEngine:
         images, ctx, actions = split_batch(batch)
         with self.autocast():
             loss_bt, aux = self.model.train_forward(images, ctx, actions, with_aux=False)
+        nll = aux.get("action_nll")
+        self.last_nll = nll.mean() if nll is not None else None
         return loss_bt.mean(), aux
 
     def _step_body(self, batch: Dict) -> torch.Tensor:
@@ -391,6 +420,7 @@ class TrainEngine:
         self.micro_step += 1
         if final:
             self._window_end()
+        self.last_nll = self._static_nll.clone() if self._static_nll is not None else None
         return self._static_loss.clone()
 
     def flush_window(self) -> bool:
@@ -420,6 +450,7 @@ class TrainEngine:
         opt.step_count += 1
         opt._dev_step = opt.step_count
         self.global_step += 1
+        self.last_nll = self._static_nll.clone() if self._static_nll is not None else None
         return self._static_loss.clone()
 
     def _capture_failed(self, e: Exception):
@@ -435,6 +466,9 @@ class TrainEngine:
         self.optimizer.sync_device_state()
         g = torch.cuda.CUDAGraph()
         steps_before = self.optimizer.step_count
+        # the capture records the step without running it: the nll tensor that its forward_loss leaves in last_nll is
+        # unwritten graph memory until a replay, so last_nll keeps the eager step's figure, capture failed or not
+        nll_eager = self.last_nll
         try:
             with torch.cuda.graph(g, capture_error_mode="relaxed" if "relaxed1" in _DP_DIAG else "global"):
                 if self.accumulate_grad_batches > 1:
@@ -446,7 +480,9 @@ class TrainEngine:
             # fallback continues from the right Adam step and re-syncs the device copy)
             self.optimizer.step_count = steps_before
             self.optimizer._dev_step = None
+            nll_static, self.last_nll = self.last_nll, nll_eager
         self.optimizer.sync_device_state()
+        self._static_nll = nll_static
         self._graph = g
 
     # ------------------------------------------------------------------ hipGraph data-parallel step
@@ -463,6 +499,7 @@ class TrainEngine:
         self.optimizer.step(grad_scale=self.ddp.grad_scale)
         self._guard_buffers()
         self.global_step += 1
+        self.last_nll = self._static_nll.clone() if self._static_nll is not None else None
         return self._static_loss.clone()
 
     def _replay_segments(self, launch: bool = True):
@@ -547,6 +584,7 @@ class TrainEngine:
         side.wait_stream(torch.cuda.current_stream(self.device))
         seg = SegmentedCapture(side, mode="global" if "globalseg" in _DP_DIAG else "relaxed")
         seg.expected_last = len(self.ddp.buckets)
+        nll_eager = self.last_nll                    # as in _capture: the captured forward's nll is not yet written
         try:
             with torch.cuda.stream(side):
                 seg.begin()
@@ -563,10 +601,13 @@ class TrainEngine:
                 # buckets that never completed (a param without a gradient)
                 self.flat.gather_grads(accumulate=self.ddp.accumulate)
                 self._static_loss = loss.detach()
+                self._static_nll = self.last_nll
                 seg.end(extra_buckets=rest)
         except BaseException:
             seg.abort()
             raise
+        finally:
+            self.last_nll = nll_eager
         torch.cuda.current_stream(self.device).wait_stream(side)
         torch.cuda.synchronize(self.device)
         self._segments = seg
@@ -612,7 +653,9 @@ class TrainEngine:
                         ema=(opt.ema.clone() if opt.ema is not None else None),
                         ema_state=(opt.ema_state.clone() if opt.ema_state is not None else None),
                         lr_base=(opt.lr_base.clone() if opt.lr_base is not None else None),
-                        sched_state=(opt.sched_state.clone() if opt.sched_state is not None else None))
+                        sched_state=(opt.sched_state.clone() if opt.sched_state is not None else None),
+                        hits=(self.token_counters.clone() if self.token_counters is not None else None),
+                        nll=(self.last_nll.clone() if self.last_nll is not None else None))
 
     def _restore(self, s: Dict):
         from ..ops import rng as _rng
@@ -640,7 +683,10 @@ class TrainEngine:
             if s["lr_base"] is not None:
                 opt.lr_base.copy_(s["lr_base"])
                 opt.sched_state.copy_(s["sched_state"])
+            if s["hits"] is not None:
+                self.token_counters.copy_(s["hits"])
         self.micro_step, self.stepped = s["micro"], s["stepped"]
+        self.last_nll = s["nll"].clone() if s["nll"] is not None else None
         opt.step_count, opt._dev_step, opt._dev_groups = s["step"], s["dev_step"], s["dev_groups"]
         if s["rng"] is not None:
             torch.cuda.set_rng_state(s["rng"], self.device)
@@ -717,6 +763,17 @@ class TrainEngine:
         self.model.eval()
         loss, _ = self.forward_loss(batch)
         return loss.detach()
+
+    def read_token_counters(self, reset: bool = True) -> Optional[torch.Tensor]:
+        """This rank's {hits, rows} per action-token slot since the last read, int64 [A, 2] on the host side of a sync
+        (None with ``token_accuracy`` off); ``reset`` zeroes the device counters, in place, so a captured graph keeps
+        adding to the same memory."""
+        if self.token_counters is None:
+            return None
+        out = self.token_counters.clone()
+        if reset:
+            self.token_counters.zero_()
+        return out
 
     def epoch_end(self):
         self.scheduler.step()

@@ -36,6 +36,14 @@ and learning rates -- into the same group layout only: the resumed run's flags m
 With the engine's ``lr_schedule`` the ``log_every_n_steps`` log point also logs ``lr-Adam`` (and ``lr/<group>`` with
 several groups) as the last applied update used them, read back from the device at the point that already synchronises
 for the loss; the per-epoch ``lr-Adam`` stays the base learning rate that ``MultiStepLR`` scales.
+
+With the engine's ``label_smoothing`` / ``z_loss`` the logged training loss is the regularised objective, so each log
+point also logs ``train_nll_step``, the plain CE of the same batches; ``eval_loss`` / ``test_loss`` are the plain CE in
+any case (the objective applies in training mode only).  With the engine's ``token_accuracy`` each log point logs
+``train_acc_step`` = hits / rows of the action tokens since the last log point, summed over ranks (one more small
+all-reduce), every validation logs ``eval_acc`` / ``test_acc`` (and ``..._ema`` where the EMA pass runs), and each of
+these comes with its per-slot values ``<name>/tok0 .. tok{A-1}``.  The device counters are zeroed at each read; what
+the training steps counted before a validation is set aside and put back after it.
 """
 from __future__ import annotations
 
@@ -83,6 +91,11 @@ class Trainer:
         self.last_ema_loss = None                # validate(): loss on the averaged weights (engine EMA on)
         if getattr(engine.optimizer, "ema", None) is not None:
             self.history["eval_loss_ema"] = []
+        self.acc_on = getattr(engine, "token_counters", None) is not None
+        self.nll_on = bool(getattr(engine, "regularised", False))
+        self.last_acc: Dict[str, float] = {}     # validate(): the accuracy metrics it logged (token_accuracy on)
+        if self.acc_on:
+            self.history["eval_acc"] = []
         self.graph_checked = False
         self.graph_check = None
 
@@ -103,6 +116,19 @@ class Trainer:
                          torch.tensor(float(count), dtype=torch.float64, device=total.device)])
         t = pdist.all_reduce_mean(t)
         return float(t[0] / t[1]) if float(t[1]) > 0 else float("nan")
+
+    def _acc_metrics(self, name: str) -> Dict[str, float]:
+        """Read and zero the engine's token counters: ``{name: hits / rows, name/tok<a>: per slot}`` over all ranks
+        (the mean over ranks of both columns: their ratio is that of the sums).  Empty without rows."""
+        c = pdist.all_reduce_mean(self.engine.read_token_counters().double())
+        hits, rows = c[:, 0], c[:, 1]
+        if float(rows.sum()) <= 0:
+            return {}
+        out = {name: float(hits.sum() / rows.sum())}
+        for a in range(c.shape[0]):
+            if float(rows[a]) > 0:
+                out[f"{name}/tok{a}"] = float(hits[a] / rows[a])
+        return out
 
     def _log(self, metrics, step=None):
         step = self.engine.global_step if step is None else step
@@ -178,12 +204,24 @@ class Trainer:
         """Mean loss over ``loader`` with the live weights (the return value).  With the engine's EMA on the pass
         runs once more on the averaged weights (``TrainEngine.ema_weights``) and logs ``<name>_ema``; the value is
         kept in ``last_ema_loss``."""
+        acc_name = name[:-len("_loss")] + "_acc" if name.endswith("_loss") else name + "_acc"
+        self.last_acc = {}
+        # what the training steps counted since the last log point waits aside while the passes below count
+        held = self.engine.read_token_counters() if self.acc_on else None
         loss = self._eval_mean(loader, limit)
+        if self.acc_on:
+            self.last_acc.update(self._acc_metrics(acc_name))
         self.last_ema_loss = None
         if getattr(self.engine.optimizer, "ema", None) is not None:
             with self.engine.ema_weights():
                 self.last_ema_loss = self._eval_mean(loader, limit)
             self._log({name + "_ema": self.last_ema_loss})
+            if self.acc_on:
+                self.last_acc.update(self._acc_metrics(acc_name + "_ema"))
+        if self.acc_on:
+            self.engine.token_counters.add_(held)
+            if self.last_acc:
+                self._log(self.last_acc)
         return loss
 
     def fit(self, train_loader: Iterable, val_loader: Optional[Iterable] = None):
@@ -221,6 +259,7 @@ class Trainer:
             if len(e.lrs) > 1:
                 self._log({f"lr/{name}": v for name, v in e.lrs.items()})
             total, n, window, wn = None, 0, None, 0
+            nwindow = None                           # plain CE of the window's batches (regularised objective)
             wsteps = 0                               # optimizer steps since the last log point (wn counts batches)
             samples = 0
             opt = e.optimizer
@@ -233,7 +272,7 @@ class Trainer:
 
             def log_point():
                 # after a train_step (or the epoch-end flush) that applied the optimizer
-                nonlocal window, wn, wcount, wsteps
+                nonlocal window, wn, wcount, wsteps, nwindow
                 wsteps += 1
                 if e.global_step % self.log_every == 0:
                     step_loss = self._mean_across(window, wcount if skip_on else wn)
@@ -250,6 +289,10 @@ class Trainer:
                     if clip_on:
                         metrics.update(grad_norm=float(opt.last_grad_norm), clipped_steps=opt.clipped_steps,
                                        skipped_steps=opt.skipped_steps)
+                    if self.nll_on and nwindow is not None:
+                        metrics["train_nll_step"] = self._mean_across(nwindow, wcount if skip_on else wn)
+                    if self.acc_on:
+                        metrics.update(self._acc_metrics("train_acc_step"))
                     lr_shown = e.lr
                     if sched_on:
                         # the scheduled values of the last applied update, from the device (this point has synchronised)
@@ -258,7 +301,7 @@ class Trainer:
                         if len(now) > 1:
                             metrics.update({f"lr/{name}": v for name, v in now.items()})
                     self._log(metrics)
-                    window, wn, wcount, wsteps = None, 0, None, 0
+                    window, wn, wcount, wsteps, nwindow = None, 0, None, 0, None
                     if self.verbose:
                         extra = (f" grad_norm {metrics['grad_norm']:.4g} clipped {metrics['clipped_steps']} "
                                  f"skipped {metrics['skipped_steps']}") if clip_on else ""
@@ -269,12 +312,17 @@ class Trainer:
                 loss = e.train_step(batch)
                 if e.graph and not self.graph_checked and (e._graph is not None or e._segments is not None):
                     self._check_graph(batch)
+                nll = e.last_nll.detach() if self.nll_on and e.last_nll is not None else None
                 if skip_on:
                     fin = torch.isfinite(loss)
                     one = fin.to(torch.float32)
                     loss = torch.where(fin, loss, torch.zeros_like(loss))
                     tcount = one if tcount is None else tcount + one
                     wcount = one if wcount is None else wcount + one
+                    if nll is not None:
+                        nll = torch.where(fin, nll, torch.zeros_like(nll))
+                if nll is not None:
+                    nwindow = nll if nwindow is None else nwindow + nll
                 total = loss if total is None else total + loss
                 window = loss if window is None else window + loss
                 n += 1
@@ -304,6 +352,8 @@ class Trainer:
             self._log(metrics)
             if val_loader is not None and self.last_ema_loss is not None:
                 metrics["eval_loss_ema"] = self.last_ema_loss        # validate() logged it already
+            if val_loader is not None and self.last_acc:
+                metrics.update(self.last_acc)                        # likewise
             for k in self.history:
                 if k in metrics:
                     self.history[k].append(metrics[k])

@@ -39,6 +39,47 @@ from .image_tokenizer import RT1ImageTokenizer
 from .transformer import Transformer, action_prediction_positions, rt1_attention_mask
 
 
+def checked_objective(label_smoothing, z_loss) -> Tuple[float, float]:
+    """``(label_smoothing, z_loss)`` as floats; ValueError unless ``0 <= label_smoothing < 1`` and ``z_loss >= 0``,
+    both finite (NaN fails every comparison)."""
+    ok = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool)
+    if not ok(label_smoothing) or not (0.0 <= label_smoothing < 1.0):
+        raise ValueError(f"label_smoothing must be a number in [0, 1), got {label_smoothing!r}")
+    if not ok(z_loss) or not (0.0 <= z_loss < float("inf")):
+        raise ValueError(f"z_loss must be a finite number >= 0, got {z_loss!r}")
+    return float(label_smoothing), float(z_loss)
+
+
+def token_losses(logits: torch.Tensor, targets: torch.Tensor, label_smoothing: float = 0.0, z_loss: float = 0.0):
+    """Per-row training objective of ``logits`` (R, V) against ``targets`` (R,) and the plain CE next to it:
+
+        loss = (1 - eps) nll + eps mean_c(-log p_c) + zeta logsumexp(z)^2
+
+    (``F.cross_entropy(label_smoothing=eps)``: the smoothing mass goes to all V classes, the target included; the PaLM
+    z-loss).  -> ``(loss, nll)``; with both options 0 the loss is the plain CE and ``nll`` is None."""
+    nll = F.cross_entropy(logits, targets, reduction="none")
+    if label_smoothing == 0.0 and z_loss == 0.0:
+        return nll, None
+    loss = nll
+    if label_smoothing != 0.0:
+        loss = F.cross_entropy(logits, targets, reduction="none", label_smoothing=label_smoothing)
+    if z_loss != 0.0:
+        loss = loss + z_loss * torch.logsumexp(logits, dim=-1) ** 2
+    return loss, nll.detach()
+
+
+def token_hits_torch_(counters: torch.Tensor, pred: torch.Tensor, targets: torch.Tensor) -> torch.Tensor:
+    """``counters`` (int64 [A, 2]) += {rows with pred == target, rows} per action-token slot ``r % A`` of the flattened
+    rows, in place: the torch form of the ``head_token_hits_`` kernel (CPU and the torch backend)."""
+    A = counters.shape[0]
+    p, t = pred.reshape(-1), targets.reshape(-1)
+    slot = torch.arange(p.numel(), device=p.device) % A
+    hit = (p.long() == t.long()).to(torch.int64)
+    counters[:, 0].index_add_(0, slot, hit)
+    counters[:, 1].index_add_(0, slot, torch.ones_like(hit))
+    return counters
+
+
 class TransformerNetwork(nn.Module):
     def __init__(self, input_tensor_space: spaces.Dict, output_tensor_space: spaces.Dict,
                  train_step_counter: int = 0, vocab_size: int = 256, token_embedding_size: int = 512,
@@ -96,6 +137,13 @@ class TransformerNetwork(nn.Module):
         })
         # kernel hooks installed by ops.install(); None = eager torch path
         self.fused = None
+        # training objective (token_losses; applied only while self.training: eval scores the plain CE) and token
+        # accuracy.  Plain attributes, neither parameters nor buffers: the checkpoint layout does not know them.
+        self.label_smoothing = 0.0
+        self.z_loss = 0.0
+        self.track_token_accuracy = False
+        self.token_counters: Optional[torch.Tensor] = None   # int64 [A, 2] {hits, rows} per slot, owned by the engine
+        self._last_nll = None
 
     # ------------------------------------------------------------------ accessors
     @property
@@ -154,12 +202,21 @@ class TransformerNetwork(nn.Module):
             return self.fused.action_logits(self, hidden, positions)
         return self._transformer._output_tokens(hidden[:, positions])
 
+    def objective(self) -> Tuple[float, float]:
+        """``(label_smoothing, z_loss)`` of this forward: the attributes while training, ``(0, 0)`` in eval mode, so
+        every validation figure stays the plain CE."""
+        if not self.training:
+            return 0.0, 0.0
+        return checked_objective(self.label_smoothing, self.z_loss)
+
     def action_loss(self, logits: torch.Tensor, targets: torch.Tensor, b: int, t: int) -> torch.Tensor:
-        """CE(reduction=none) / (b*t*L), mean over the A tokens -> (b, t)  (``:314-322``)."""
+        """loss(reduction=none) / (b*t*L), mean over the A tokens -> (b, t)  (``:314-322``); the loss is the CE, or
+        ``token_losses`` under ``objective()``, and then ``_last_nll`` holds the plain CE normalised the same way."""
         if self.fused is not None:
             return self.fused.action_loss(self, logits, targets, b, t)
-        ce = F.cross_entropy(logits.float().reshape(-1, logits.shape[-1]), targets.reshape(-1), reduction="none")
+        ce, nll = token_losses(logits.float().reshape(-1, logits.shape[-1]), targets.reshape(-1), *self.objective())
         num_items = float(b * t) * self._single_time_step_num_tokens
+        self._last_nll = None if nll is None else (nll.view(b, t, self._tokens_per_action) / num_items).mean(dim=-1)
         return (ce.view(b, t, self._tokens_per_action) / num_items).mean(dim=-1)
 
     # ------------------------------------------------------------------ training
@@ -174,10 +231,13 @@ class TransformerNetwork(nn.Module):
             targets = self._action_tokenizer.tokenize(actions)                   # (b, t, A)
         image_tokens = self.tokenize_images(images, context, shift)
         hidden = self.transformer_hidden(self.assemble_tokens(image_tokens.to(self._compute_dtype(image_tokens))))
-        preds = None
+        preds = hits_from = None
+        self._last_nll = None
         if self.fused is not None and self.fused.fused_head:
             # one HIP kernel: gather + logits + CE + argmax (ops/head.py)
-            loss, preds = self.fused.head_and_loss(self, hidden, self._predicted_positions, targets, b, t, targets32)
+            loss, preds, self._last_nll = self.fused.head_and_loss(self, hidden, self._predicted_positions, targets, b,
+                                                                   t, targets32)
+            hits_from = preds                    # int32, what the hit-count kernel reads
             preds = preds.view(b, t, self._tokens_per_action).long()
         else:
             logits = self.action_logits(hidden, self._predicted_positions)        # (b, T*A, V)
@@ -186,9 +246,21 @@ class TransformerNetwork(nn.Module):
         # stream of the first step (breaks hipGraph capture); the reference-style forward() re-attaches it
         self._loss = loss.detach()
         aux: Dict[str, Any] = {"action_labels": targets, "action_loss": self._loss}
-        if with_aux:
+        if self._last_nll is not None:
+            aux["action_nll"] = self._last_nll.detach()       # the plain CE under a regularised objective
+        track = self.track_token_accuracy and self.token_counters is not None
+        if with_aux or track:
             if preds is None:
                 preds = logits.detach().view(b, t, self._tokens_per_action, -1).argmax(dim=-1)
+        if track:
+            with torch.no_grad():
+                if self.fused is not None and self.token_counters.is_cuda:
+                    # the hip backend counts with its kernel on every route (rows converted to int32 where needed)
+                    self.fused.token_hits(self.token_counters, hits_from if hits_from is not None else preds,
+                                          targets32 if targets32 is not None else targets)
+                else:
+                    token_hits_torch_(self.token_counters, preds, targets)
+        if with_aux:
             aux.update({"action_predictions": preds,
                         "actor_loss_mask": torch.ones(b, dtype=torch.float32, device=loss.device),
                         "predicted_tokens_for_output": preds[:, -1]})

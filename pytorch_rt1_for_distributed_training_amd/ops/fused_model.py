@@ -173,10 +173,11 @@ class FusedRT1:
         return x
 
     def action_loss(self, model, logits, targets, b, t):
-        import torch.nn.functional as F
-        ce = F.cross_entropy(logits.float().reshape(-1, logits.shape[-1]), targets.reshape(-1), reduction="none")
+        from ..models.policy import token_losses
+        loss, nll = token_losses(logits.float().reshape(-1, logits.shape[-1]), targets.reshape(-1), *model.objective())
         num_items = float(b * t) * model._single_time_step_num_tokens
-        return (ce.view(b, t, model._tokens_per_action) / num_items).mean(dim=-1)
+        model._last_nll = None if nll is None else (nll.view(b, t, model._tokens_per_action) / num_items).mean(dim=-1)
+        return (loss.view(b, t, model._tokens_per_action) / num_items).mean(dim=-1)
 
     def tokenize_actions(self, tokenizer, actions):
         """Action labels in one HIP launch (csrc/kernels/head.hip action_tokenize): -> (int64 labels, int32 copy for
@@ -195,17 +196,23 @@ class FusedRT1:
         return t64, t32
 
     def head_and_loss(self, model, hidden, positions, targets, b, t, targets32=None):
-        """Fused head: returns the reference loss (b, t) and the argmax action tokens (b, T*A)."""
-        from .head import head_ce
+        """Fused head: returns the reference loss (b, t), the argmax action tokens (b, T*A) and, under the regularised
+        objective (``model.objective()``), the plain CE with the loss's normalisation (else None)."""
+        from .head import head_loss
         key = (positions.data_ptr(), positions.device)
         pos = self._positions.get(key)
         if pos is None:
             pos = positions.to(torch.int32).contiguous()
             self._positions[key] = pos
-        ce, pred = head_ce(model._transformer._output_tokens, hidden, pos, targets, targets32)
+        eps, zeta = model.objective()
+        rows, pred, nll = head_loss(model._transformer._output_tokens, hidden, pos, targets, targets32, eps, zeta)
         num_items = float(b * t) * model._single_time_step_num_tokens
-        loss = (ce.view(b, t, model._tokens_per_action) / num_items).mean(dim=-1)
-        return loss, pred.view(b, -1)
+        norm = lambda r: (r.view(b, t, model._tokens_per_action) / num_items).mean(dim=-1)
+        return norm(rows), pred.view(b, -1), (norm(nll) if nll is not None else None)
+
+    def token_hits(self, counters, pred, targets):
+        from .head import token_hits_
+        return token_hits_(counters, pred, targets)
 
     def action_logits(self, model, hidden, positions):
         with self._autocast():

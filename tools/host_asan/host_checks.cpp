@@ -181,6 +181,22 @@ int main(int argc, char** argv) {
     for (int p : {1, 64, 100, 120, 225, 256, 257, 1000}) rt1_tl_supported(p, 512, 64, 8);
     EXPECT(!rt1_tl_supported(257, 512, 64, 8));
     for (int v : {2, 128, 256, 512, 1024, 4096}) rt1_head_ce_supported(v, 512);
+    // the regularised head refuses label smoothing outside [0, 1), a negative or non-finite z-loss and an unknown
+    // vocabulary, and the hit counter a slot count outside [1, 32] or no rows, all before any launch
+    {
+        const int bad = (int)hipErrorInvalidValue;
+        const float nan = std::strtof("nan", nullptr), inf = std::strtof("inf", nullptr);
+        const float opts[][2] = {{1.f, 0.f}, {-0.1f, 0.f}, {0.f, -1e-4f}, {nan, 0.f}, {0.f, nan}, {0.f, inf}, {inf, 0.f}};
+        for (const auto& o : opts)
+            EXPECT(rt1_head_ce_loss_fwd(nullptr, nullptr, nullptr, nullptr, nullptr, 16, 1, 1, 256, o[0], o[1], nullptr,
+                                        nullptr, nullptr, nullptr, nullptr, nullptr) == bad);
+        EXPECT(rt1_head_ce_loss_fwd(nullptr, nullptr, nullptr, nullptr, nullptr, 16, 1, 1, 128, 0.1f, 0.f, nullptr,
+                                    nullptr, nullptr, nullptr, nullptr, nullptr) == bad);
+        EXPECT(rt1_head_ce_loss_fwd(nullptr, nullptr, nullptr, nullptr, nullptr, 0, 1, 1, 256, 0.1f, 0.f, nullptr,
+                                    nullptr, nullptr, nullptr, nullptr, nullptr) == bad);
+        for (int a : {0, -1, 33}) EXPECT(rt1_head_token_hits(nullptr, nullptr, 16, a, nullptr, nullptr) == bad);
+        EXPECT(rt1_head_token_hits(nullptr, nullptr, 0, 3, nullptr, nullptr) == bad);
+    }
     // gradient-norm grid: 1 <= P <= cap for every n >= 1 (no overflow in the grid arithmetic), 0 for n <= 0
     {
         const int cap = 2048;
