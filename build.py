@@ -3,9 +3,10 @@
 
 No torch cpp_extension / hipify: every ``csrc/kernels/*.hip`` is a plain HIP
 translation unit compiled by ``hipcc --offload-arch=gfx950`` (no torch headers,
-seconds per file); ``csrc/bindings.cpp`` is the only unit that includes torch;
-the objects are linked with ``hipcc -shared`` against the torch libraries that
-are already loaded in-process.  Incremental: an object is rebuilt only when its
+seconds per file); only the host units ``csrc/*.cpp`` (``bindings.cpp``,
+``bindings_head.cpp``, ``comm.cpp``) include torch; the objects are linked
+with ``hipcc -shared`` against the torch libraries that are already loaded
+in-process.  Incremental: an object is rebuilt only when its
 source or a header changed.  The ``.so`` lands inside the package so it travels
 with the repo snapshot to the GPU box.
 

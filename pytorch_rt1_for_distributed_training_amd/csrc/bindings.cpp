@@ -48,17 +48,32 @@ void check_dev(const at::Tensor& t, const char* name, at::ScalarType dt) {
     TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
 }
 
-void flat_adam(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v, double lr, double beta1, double beta2,
-               double eps, double weight_decay, double step_size, double inv_sqrt_bc2, double grad_scale) {
+bool aligned16(const at::Tensor& t) { return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0; }
+
+bool overlaps(const at::Tensor& a, const at::Tensor& b) {
+    const char* a0 = static_cast<const char*>(a.data_ptr());
+    const char* b0 = static_cast<const char*>(b.data_ptr());
+    return a0 < b0 + b.nbytes() && b0 < a0 + a.nbytes();
+}
+
+// the four main buffers of the fused Adam: fp32, contiguous, one size (returned), 16-byte aligned, on one device
+int64_t check_adam_buffers(const at::Tensor& p, const at::Tensor& g, const at::Tensor& m, const at::Tensor& v,
+                           const char* W) {
     check_dev(p, "param", at::kFloat);
     check_dev(g, "grad", at::kFloat);
     check_dev(m, "exp_avg", at::kFloat);
     check_dev(v, "exp_avg_sq", at::kFloat);
     const int64_t n = p.numel();
-    TORCH_CHECK(g.numel() == n && m.numel() == n && v.numel() == n, "flat_adam: size mismatch");
-    TORCH_CHECK(reinterpret_cast<uintptr_t>(p.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(g.data_ptr()) % 16 == 0 &&
-                reinterpret_cast<uintptr_t>(m.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(v.data_ptr()) % 16 == 0,
-                "flat_adam: buffers must be 16-byte aligned");
+    TORCH_CHECK(g.numel() == n && m.numel() == n && v.numel() == n, W, ": sizes");
+    TORCH_CHECK(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v), W, ": buffers must be 16-byte aligned");
+    TORCH_CHECK(g.device() == p.device() && m.device() == p.device() && v.device() == p.device(), W,
+                ": tensors on different devices");
+    return n;
+}
+
+void flat_adam(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v, double lr, double beta1, double beta2,
+               double eps, double weight_decay, double step_size, double inv_sqrt_bc2, double grad_scale) {
+    const int64_t n = check_adam_buffers(p, g, m, v, "flat_adam");
     check_launch(rt1_flat_adam(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), n,
                                (float)lr, (float)beta1, (float)beta2, (float)eps, (float)weight_decay,
                                (float)step_size, (float)inv_sqrt_bc2, (float)grad_scale, cur_stream()),
@@ -75,26 +90,6 @@ const uint32_t* seed_ptr(const OptT& t) {
     TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kInt && t->numel() >= 1, "seed_dev must be a GPU int32 tensor");
     return reinterpret_cast<const uint32_t*>(t->data_ptr());
 }
-
-void flat_adam_dev(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v, at::Tensor state, double beta1,
-                   double beta2, double eps, double weight_decay, double grad_scale) {
-    check_dev(p, "param", at::kFloat);
-    check_dev(g, "grad", at::kFloat);
-    check_dev(m, "exp_avg", at::kFloat);
-    check_dev(v, "exp_avg_sq", at::kFloat);
-    check_dev(state, "state", at::kFloat);
-    const int64_t n = p.numel();
-    TORCH_CHECK(g.numel() == n && m.numel() == n && v.numel() == n && state.numel() >= 2, "flat_adam_dev: sizes");
-    TORCH_CHECK(reinterpret_cast<uintptr_t>(p.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(g.data_ptr()) % 16 == 0 &&
-                reinterpret_cast<uintptr_t>(m.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(v.data_ptr()) % 16 == 0,
-                "flat_adam_dev: buffers must be 16-byte aligned");
-    check_launch(rt1_flat_adam_dev(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(),
-                                   n, state.data_ptr<float>(), (float)beta1, (float)beta2, (float)eps,
-                                   (float)weight_decay, (float)grad_scale, cur_stream()),
-                 "flat_adam_dev");
-}
-
-bool aligned16(const at::Tensor& t) { return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0; }
 
 void check_clip_state(const at::Tensor& cs, const char* what) {
     check_dev(cs, "clip_state", at::kFloat);
@@ -140,114 +135,54 @@ void buffer_guard_(at::Tensor buf, at::Tensor shadow, at::Tensor clip_state) {
                                   cur_stream()), "buffer_guard_");
 }
 
-void flat_adam_clip_dev(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v, at::Tensor state,
-                        at::Tensor clip_state, double beta1, double beta2, double eps, double weight_decay,
-                        double grad_scale) {
-    check_dev(p, "param", at::kFloat);
-    check_dev(g, "grad", at::kFloat);
-    check_dev(m, "exp_avg", at::kFloat);
-    check_dev(v, "exp_avg_sq", at::kFloat);
-    check_dev(state, "state", at::kFloat);
-    check_clip_state(clip_state, "flat_adam_clip_dev");
-    const int64_t n = p.numel();
-    TORCH_CHECK(g.numel() == n && m.numel() == n && v.numel() == n && state.numel() >= 2, "flat_adam_clip_dev: sizes");
-    TORCH_CHECK(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v),
-                "flat_adam_clip_dev: buffers must be 16-byte aligned");
-    check_launch(rt1_flat_adam_clip_dev(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(),
-                                        v.data_ptr<float>(), n, state.data_ptr<float>(), clip_state.data_ptr<float>(),
-                                        (float)beta1, (float)beta2, (float)eps, (float)weight_decay, (float)grad_scale,
-                                        cur_stream()),
-                 "flat_adam_clip_dev");
-}
+bool given(const OptT& t) { return t.has_value() && t->defined(); }
 
-bool overlaps(const at::Tensor& a, const at::Tensor& b) {
-    const char* a0 = static_cast<const char*>(a.data_ptr());
-    const char* b0 = static_cast<const char*>(b.data_ptr());
-    return a0 < b0 + b.nbytes() && b0 < a0 + a.nbytes();
-}
-
-// fused Adam + exponential moving average of the weights; clip_state = None: the plain form, else the clip form
-void flat_adam_ema_dev(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v, at::Tensor ema, at::Tensor state,
-                       at::Tensor ema_state, const OptT& clip_state, double beta1, double beta2, double eps,
-                       double weight_decay, double grad_scale, double one_minus_decay, bool warmup) {
-    check_dev(p, "param", at::kFloat);
-    check_dev(g, "grad", at::kFloat);
-    check_dev(m, "exp_avg", at::kFloat);
-    check_dev(v, "exp_avg_sq", at::kFloat);
-    check_dev(ema, "ema", at::kFloat);
+// The fused Adam with {step, lr} on the device in every form (csrc/kernels/adam.hip); an absent option is None.
+// clip_state fp32[8]: the verdict to obey.  ema + ema_state fp32[4]: the average of the weights, in the same launch.
+// group_state fp32[4 * G] = G x {lr, wd, 0, 0} + chunk_group uint8[n / 64]: lr / weight_decay per parameter group, in
+// which case weight_decay and state[1] are not read.
+void flat_adam_dev(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v, at::Tensor state, const OptT& ema,
+                   const OptT& ema_state, const OptT& clip_state, const OptT& group_state, const OptT& chunk_group,
+                   double beta1, double beta2, double eps, double weight_decay, double grad_scale,
+                   double one_minus_decay, bool warmup) {
+    const char* W = "flat_adam_dev";
+    const int64_t n = check_adam_buffers(p, g, m, v, W);
     check_dev(state, "state", at::kFloat);
-    check_dev(ema_state, "ema_state", at::kFloat);
+    TORCH_CHECK(state.numel() >= 2, W, ": sizes");
+    TORCH_CHECK(state.device() == p.device(), W, ": tensors on different devices");
     const float* cs = nullptr;
-    if (clip_state.has_value() && clip_state->defined()) {
-        check_clip_state(*clip_state, "flat_adam_ema_dev");
-        TORCH_CHECK(clip_state->device() == p.device(), "flat_adam_ema_dev: clip_state on another device");
-        cs = clip_state->data_ptr<float>();
-    }
-    const int64_t n = p.numel();
-    TORCH_CHECK(g.numel() == n && m.numel() == n && v.numel() == n && ema.numel() == n && state.numel() >= 2,
-                "flat_adam_ema_dev: sizes");
-    TORCH_CHECK(ema_state.numel() >= 4 && aligned16(ema_state),
-                "flat_adam_ema_dev: ema_state must be fp32[4], 16-byte aligned");
-    TORCH_CHECK(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) && aligned16(ema),
-                "flat_adam_ema_dev: buffers must be 16-byte aligned");
-    TORCH_CHECK(g.device() == p.device() && m.device() == p.device() && v.device() == p.device() &&
-                ema.device() == p.device() && state.device() == p.device() && ema_state.device() == p.device(),
-                "flat_adam_ema_dev: tensors on different devices");
-    TORCH_CHECK(!overlaps(ema, p) && !overlaps(ema, g) && !overlaps(ema, m) && !overlaps(ema, v) &&
-                !overlaps(ema_state, state) && !overlaps(ema_state, ema),
-                "flat_adam_ema_dev: ema / ema_state must not alias another buffer");
-    TORCH_CHECK(one_minus_decay > 0.0 && one_minus_decay <= 1.0, "flat_adam_ema_dev: one_minus_decay must be in (0, 1]");
-    check_launch(rt1_flat_adam_ema_dev(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(),
-                                       v.data_ptr<float>(), ema.data_ptr<float>(), n, state.data_ptr<float>(), cs,
-                                       ema_state.data_ptr<float>(), (float)beta1, (float)beta2, (float)eps,
-                                       (float)weight_decay, (float)grad_scale, (float)one_minus_decay, warmup ? 1 : 0,
-                                       cur_stream()),
-                 "flat_adam_ema_dev");
-}
-
-// fused Adam with lr / weight_decay per parameter group (flat_adam_groups_kernel): ema / ema_state = None: no average,
-// clip_state = None: no verdict.  chunk_group uint8[n / 64], group_state fp32[4 * G] = G x {lr, wd, 0, 0}.
-void flat_adam_groups_dev(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v, const OptT& ema, at::Tensor state,
-                          at::Tensor group_state, at::Tensor chunk_group, const OptT& ema_state,
-                          const OptT& clip_state, double beta1, double beta2, double eps, double grad_scale,
-                          double one_minus_decay, bool warmup) {
-    const char* W = "flat_adam_groups_dev";
-    check_dev(p, "param", at::kFloat);
-    check_dev(g, "grad", at::kFloat);
-    check_dev(m, "exp_avg", at::kFloat);
-    check_dev(v, "exp_avg_sq", at::kFloat);
-    check_dev(state, "state", at::kFloat);
-    check_dev(group_state, "group_state", at::kFloat);
-    check_dev(chunk_group, "chunk_group", at::kByte);
-    const int64_t n = p.numel();
-    TORCH_CHECK(n > 0 && n % 64 == 0, W, ": param has ", n, " elements, not a positive multiple of 64");
-    TORCH_CHECK(g.numel() == n && m.numel() == n && v.numel() == n && state.numel() >= 2, W, ": sizes");
-    TORCH_CHECK(chunk_group.numel() == n / 64, W, ": chunk_group has ", chunk_group.numel(), " entries, expected ",
-                n / 64, " (one per 64 elements)");
-    const int64_t G = group_state.numel() / 4;
-    TORCH_CHECK(group_state.numel() % 4 == 0 && G >= 1 && G <= 16, W, ": group_state has ", group_state.numel(),
-                " entries, expected 4 per group for 1 to 16 groups");
-    TORCH_CHECK(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) && aligned16(group_state), W,
-                ": buffers and group_state must be 16-byte aligned");
-    TORCH_CHECK(g.device() == p.device() && m.device() == p.device() && v.device() == p.device() &&
-                state.device() == p.device(), W, ": tensors on different devices");
-    TORCH_CHECK(group_state.device() == p.device(), W, ": group_state on another device");
-    TORCH_CHECK(chunk_group.device() == p.device(), W, ": chunk_group on another device");
-    TORCH_CHECK(!overlaps(chunk_group, p) && !overlaps(chunk_group, m) && !overlaps(chunk_group, v) &&
-                !overlaps(group_state, p) && !overlaps(group_state, m) && !overlaps(group_state, v),
-                W, ": chunk_group / group_state must not alias a buffer the kernel writes");
-    const float* cs = nullptr;
-    if (clip_state.has_value() && clip_state->defined()) {
+    if (given(clip_state)) {
         check_clip_state(*clip_state, W);
         TORCH_CHECK(clip_state->device() == p.device(), W, ": clip_state on another device");
         cs = clip_state->data_ptr<float>();
     }
+    const bool groups = given(group_state);
+    TORCH_CHECK(groups == given(chunk_group), W, ": group_state and chunk_group go together (both or neither)");
+    const float* gst = nullptr;
+    const uint8_t* tab = nullptr;
+    int64_t G = 0;
+    if (groups) {
+        check_dev(*group_state, "group_state", at::kFloat);
+        check_dev(*chunk_group, "chunk_group", at::kByte);
+        TORCH_CHECK(n > 0 && n % 64 == 0, W, ": param has ", n, " elements, not a positive multiple of 64");
+        TORCH_CHECK(chunk_group->numel() == n / 64, W, ": chunk_group has ", chunk_group->numel(),
+                    " entries, expected ", n / 64, " (one per 64 elements)");
+        G = group_state->numel() / 4;
+        TORCH_CHECK(group_state->numel() % 4 == 0 && G >= 1 && G <= 16, W, ": group_state has ", group_state->numel(),
+                    " entries, expected 4 per group for 1 to 16 groups");
+        TORCH_CHECK(aligned16(*group_state), W, ": group_state must be 16-byte aligned");
+        TORCH_CHECK(group_state->device() == p.device(), W, ": group_state on another device");
+        TORCH_CHECK(chunk_group->device() == p.device(), W, ": chunk_group on another device");
+        TORCH_CHECK(!overlaps(*chunk_group, p) && !overlaps(*chunk_group, m) && !overlaps(*chunk_group, v) &&
+                    !overlaps(*group_state, p) && !overlaps(*group_state, m) && !overlaps(*group_state, v),
+                    W, ": chunk_group / group_state must not alias a buffer the kernel writes");
+        gst = group_state->data_ptr<float>();
+        tab = chunk_group->data_ptr<uint8_t>();
+    }
     float* e = nullptr;
     float* es = nullptr;
-    const bool has_ema = ema.has_value() && ema->defined();
-    TORCH_CHECK(has_ema == (ema_state.has_value() && ema_state->defined()), W,
-                ": ema and ema_state go together (both or neither)");
-    if (has_ema) {
+    TORCH_CHECK(given(ema) == given(ema_state), W, ": ema and ema_state go together (both or neither)");
+    if (given(ema)) {
         check_dev(*ema, "ema", at::kFloat);
         check_dev(*ema_state, "ema_state", at::kFloat);
         TORCH_CHECK(ema->numel() == n, W, ": sizes");
@@ -256,18 +191,18 @@ void flat_adam_groups_dev(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v
         TORCH_CHECK(ema->device() == p.device() && ema_state->device() == p.device(), W,
                     ": tensors on different devices");
         TORCH_CHECK(!overlaps(*ema, p) && !overlaps(*ema, g) && !overlaps(*ema, m) && !overlaps(*ema, v) &&
-                    !overlaps(*ema_state, state) && !overlaps(*ema_state, *ema) && !overlaps(*ema, chunk_group) &&
-                    !overlaps(*ema, group_state) && !overlaps(*ema_state, group_state),
+                    !overlaps(*ema_state, state) && !overlaps(*ema_state, *ema) &&
+                    !(groups && (overlaps(*ema, *chunk_group) || overlaps(*ema, *group_state) ||
+                                 overlaps(*ema_state, *group_state))),
                     W, ": ema / ema_state must not alias another buffer");
         TORCH_CHECK(one_minus_decay > 0.0 && one_minus_decay <= 1.0, W, ": one_minus_decay must be in (0, 1]");
         e = ema->data_ptr<float>();
         es = ema_state->data_ptr<float>();
     }
-    check_launch(rt1_flat_adam_groups_dev(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(),
-                                          v.data_ptr<float>(), e, n, state.data_ptr<float>(),
-                                          group_state.data_ptr<float>(), chunk_group.data_ptr<uint8_t>(), (int)G, cs,
-                                          es, (float)beta1, (float)beta2, (float)eps, (float)grad_scale,
-                                          (float)one_minus_decay, warmup ? 1 : 0, cur_stream()),
+    check_launch(rt1_flat_adam_dev(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(),
+                                   n, state.data_ptr<float>(), cs, e, es, gst, tab, (int)G, (float)beta1, (float)beta2,
+                                   (float)eps, (float)weight_decay, (float)grad_scale, (float)one_minus_decay,
+                                   warmup ? 1 : 0, cur_stream()),
                  W);
 }
 
@@ -1645,11 +1580,9 @@ void register_head(py::module_& m);
 PYBIND11_MODULE(_rt1_hip, m) {
     m.doc() = "RT-1 HIP/CDNA4 kernels (gfx950)";
     m.def("flat_adam", &flat_adam, "fused Adam/AdamW over flat fp32 buffers");
-    m.def("flat_adam_dev", &flat_adam_dev, "fused Adam/AdamW, step/lr read from a device tensor (graph-replayable)");
-    m.def("flat_adam_clip_dev", &flat_adam_clip_dev, "flat_adam_dev obeying clip_state (clip coefficient, skipped step)");
-    m.def("flat_adam_ema_dev", &flat_adam_ema_dev, "flat_adam_dev / flat_adam_clip_dev that also updates the EMA of the weights");
-    m.def("flat_adam_groups_dev", &flat_adam_groups_dev,
-          "the device-state Adam forms (plain, clip, EMA, both) with lr / weight_decay per parameter group");
+    m.def("flat_adam_dev", &flat_adam_dev,
+          "fused Adam/AdamW, step/lr read from a device tensor (graph-replayable); optionally obeying clip_state, "
+          "updating the EMA of the weights, with lr / weight_decay per parameter group");
     m.def("lr_schedule_dev", &lr_schedule_dev,
           "per-step lr schedule on the device: state[1] / group_state[g][0] <- lr_base[g] * f(effective Adam step)");
     m.def("gradnorm_partials", &gradnorm_partials, "fp64 partial sums grad_sumsq writes for n floats");

@@ -10,28 +10,21 @@ extern "C" {
 int rt1_flat_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                   float eps, float weight_decay, float step_size, float inv_sqrt_bc2, float grad_scale,
                   hipStream_t stream);
-// graph-replayable variant: state = {step, lr} on the device (the step is advanced by the caller's device op)
-int rt1_flat_adam_dev(float* p, const float* g, float* m, float* v, int64_t n, const float* state, float beta1,
-                      float beta2, float eps, float weight_decay, float grad_scale, hipStream_t stream);
-// rt1_flat_adam_dev under gradnorm.hip's clip_state: nothing is touched when ok == 0, g = (g * grad_scale) * coef
-// otherwise, Adam step = state[0] - skipped steps
-int rt1_flat_adam_clip_dev(float* p, const float* g, float* m, float* v, int64_t n, const float* state,
-                           const float* clip_state, float beta1, float beta2, float eps, float weight_decay,
-                           float grad_scale, hipStream_t stream);
-// rt1_flat_adam_dev (clip_state == nullptr) or rt1_flat_adam_clip_dev (otherwise) that also carries an exponential
-// moving average of the weights: ema += omd_t * (p_new - ema), omd_t = warmup ? max(one_minus_decay, 9 / (10 + t))
-// : one_minus_decay with t the Adam step of this call; ema_state fp32[4] <- {omd_t, t, 0, 0} of an applied update
-int rt1_flat_adam_ema_dev(float* p, const float* g, float* m, float* v, float* ema, int64_t n, const float* state,
-                          const float* clip_state, float* ema_state, float beta1, float beta2, float eps,
-                          float weight_decay, float grad_scale, float one_minus_decay, int warmup,
-                          hipStream_t stream);
-// the device-state update with lr and weight_decay per parameter group: chunk_group uint8[n / 64] names the group of
-// each 64-float chunk, group_state fp32 [G, 4] = {lr_g, wd_g, 0, 0}, 1 <= G <= 16, n % 64 == 0.  ema == nullptr:
-// no average; clip_state == nullptr: no verdict.  Group g's elements equal the ungrouped kernel's at (lr_g, wd_g).
-int rt1_flat_adam_groups_dev(float* p, const float* g, float* m, float* v, float* ema, int64_t n, const float* state,
-                             const float* group_state, const uint8_t* chunk_group, int G, const float* clip_state,
-                             float* ema_state, float beta1, float beta2, float eps, float grad_scale,
-                             float one_minus_decay, int warmup, hipStream_t stream);
+// The graph-replayable forms: state = {step, lr} on the device (the step is advanced by the caller's device op).  What
+// is optional is null when absent:
+//   clip_state   gradnorm.hip's verdict: nothing is touched when ok == 0, g = (g * grad_scale) * coef otherwise, and
+//                the Adam step is t = state[0] - skipped steps;
+//   ema          an exponential moving average of the weights carried by the same launch: ema += omd_t * (p_new - ema),
+//                omd_t = warmup ? max(one_minus_decay, 9 / (10 + t)) : one_minus_decay; ema_state fp32[4] (required
+//                with ema) <- {omd_t, t, 0, 0} of an applied update;
+//   group_state, chunk_group (both or neither)   lr and weight_decay per parameter group: chunk_group uint8[n / 64]
+//                names the group of each 64-float chunk, group_state fp32 [G, 4] = {lr_g, wd_g, 0, 0}, 1 <= G <= 16,
+//                n % 64 == 0; state[1] and weight_decay are not read.  Group g's elements equal the ungrouped update's
+//                at (lr_g, wd_g).
+int rt1_flat_adam_dev(float* p, const float* g, float* m, float* v, int64_t n, const float* state,
+                      const float* clip_state, float* ema, float* ema_state, const float* group_state,
+                      const uint8_t* chunk_group, int G, float beta1, float beta2, float eps, float weight_decay,
+                      float grad_scale, float one_minus_decay, int warmup, hipStream_t stream);
 // lr_schedule.hip: the per-step schedule factor f(t) of the effective Adam step t = state[0] - skipped steps, formed in
 // fp64 and rounded once: state[1] <- lr_base[0] * f, group_state[g][0] <- lr_base[g] * f (group_state may be nullptr),
 // sched_state fp32[4] <- {f, t, 0, 0}; nothing is written on a skipped step.  kind 0..3 = constant, linear, cosine,

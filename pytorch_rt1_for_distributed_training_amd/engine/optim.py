@@ -17,12 +17,12 @@ Lightning-format checkpoints.
 Parameter groups (``groups=[{"params", "name", "lr", "weight_decay"}, ...]``, at
 most 16): the groups are scattered through the gradient-ready-order flat buffer,
 so the group is looked up per 64-element chunk inside the one launch
-(``ops.adam.flat_adam_groups_dev_step``: ``chunk_group`` uint8 per chunk,
+(``ops.adam.flat_adam_dev_step`` given ``chunk_group`` uint8 per chunk and
 ``group_state`` fp32 ``[G, 4] = {lr, wd, 0, 0}`` on the device).  While every group
 holds the same ``(lr, weight_decay)`` -- the single default group always does --
-the step runs the ungrouped kernels, to which the grouped one is bitwise equal
+the step runs the ungrouped form, to which the grouped one is bitwise equal
 group by group; a capture with more than one group always records the grouped
-kernel, so a later scheduler step cannot invalidate the graph.
+form, so a later scheduler step cannot invalidate the graph.
 ``build_param_groups`` makes the usual groups from a model: no weight decay on
 norms, biases and embeddings, a smaller learning rate on the pretrained backbone.
 
@@ -160,7 +160,7 @@ class FlatAdam(torch.optim.Optimizer):
                 self._partials = torch.zeros(self._kernel.gradnorm_partials(flat.grad.numel()), dtype=torch.float64,
                                              device=flat.data.device)
         # exponential moving average of the trainable weights (off at 0): one more flat fp32 buffer, updated by the
-        # same launch as Adam (ops.adam.flat_adam_ema_dev_step).  ema_state is fp32[4] = {omd_t of the last applied
+        # same launch as Adam (flat_adam_dev_step given ema).  ema_state is fp32[4] = {omd_t of the last applied
         # update, its Adam step t, 0, 0} with omd = 1 - decay; under warm-up omd_t = max(omd, 9 / (10 + t)), i.e. the
         # decay min(decay, (1 + t) / (10 + t)).  BN running statistics and frozen parameters are not in the flat buffer
         # and are not averaged (torch.optim.swa_utils.AveragedModel's default).  The buffer is fp32: at decay 0.9999
@@ -214,29 +214,14 @@ class FlatAdam(torch.optim.Optimizer):
                 self._kernel.lr_schedule_dev(self.dev_state, self.lr_base, self.sched_state,
                                              group_state=self.group_state, clip_state=self.clip_state,
                                              **self.lr_schedule)
-            if grouped:
-                self._kernel.flat_adam_groups_dev_step(self.flat.data, self.flat.grad, self.exp_avg, self.exp_avg_sq,
-                                                       self.dev_state, self.group_state, self.chunk_group,
-                                                       ema=self.ema, ema_state=self.ema_state,
-                                                       clip_state=self.clip_state, beta1=b1, beta2=b2, eps=eps,
-                                                       grad_scale=grad_scale, one_minus_decay=self._omd,
-                                                       warmup=self.ema_warmup)
-                return loss
-            if self.ema_enabled:
-                self._kernel.flat_adam_ema_dev_step(self.flat.data, self.flat.grad, self.exp_avg, self.exp_avg_sq,
-                                                    self.ema, self.dev_state, self.ema_state, self.clip_state,
-                                                    beta1=b1, beta2=b2, eps=eps, weight_decay=wd,
-                                                    grad_scale=grad_scale, one_minus_decay=self._omd,
-                                                    warmup=self.ema_warmup)
-                return loss
-            if self.clip_enabled:
-                self._kernel.flat_adam_clip_dev_step(self.flat.data, self.flat.grad, self.exp_avg, self.exp_avg_sq,
-                                                     self.dev_state, self.clip_state, beta1=b1, beta2=b2, eps=eps,
-                                                     weight_decay=wd, grad_scale=grad_scale)
-                return loss
+            # one launch in every form: clip_state and ema are None when off, the groups' tensors go only if grouped
             self._kernel.flat_adam_dev_step(self.flat.data, self.flat.grad, self.exp_avg, self.exp_avg_sq,
-                                            self.dev_state, beta1=b1, beta2=b2, eps=eps, weight_decay=wd,
-                                            grad_scale=grad_scale)
+                                            self.dev_state, ema=self.ema, ema_state=self.ema_state,
+                                            clip_state=self.clip_state,
+                                            group_state=self.group_state if grouped else None,
+                                            chunk_group=self.chunk_group if grouped else None, beta1=b1, beta2=b2,
+                                            eps=eps, weight_decay=wd, grad_scale=grad_scale,
+                                            one_minus_decay=self._omd, warmup=self.ema_warmup)
             return loss
         grad = self.flat.grad
         if grad_scale != 1.0:

@@ -38,7 +38,7 @@ data parallelism only the final micro-batch all-reduces.  BN running statistics 
 shadow is the state before the window, so a skipped window rolls all of it back.
 
 ``ema_decay=d`` (0 = off, and then nothing here changes): the optimizer keeps an exponential moving average of the
-trainable weights in one more flat fp32 buffer, updated by the Adam launch itself (``ops.adam.flat_adam_ema_dev_step``:
+trainable weights in one more flat fp32 buffer, updated by the Adam launch itself (``ops.adam.flat_adam_dev_step`` given ``ema``:
 ``ema += omd_t * (p - ema)``, the warm-up schedule formed on the device from the same step the bias corrections use), so
 every step path above carries it and a skipped step leaves it untouched.  BN running statistics and the frozen
 ``_action_token_emb`` are not averaged: ``ema_weights()`` runs the averaged weights with the live BN buffers
@@ -48,7 +48,7 @@ below about ``1e-3 |ema|`` moves it by less than an ulp.
 ``no_decay_norm_bias`` / ``backbone_lr_mult`` (off / 1, and then nothing here changes): the optimizer gets up to four
 parameter groups (``engine.optim.build_param_groups``: no weight decay on norms, biases and embeddings; a smaller
 learning rate on the pretrained backbone) and the Adam launch looks the group up per 64-element chunk
-(``ops.adam.flat_adam_groups_dev_step``), on every step path above and together with clipping and the EMA.  Each group's
+(``ops.adam.flat_adam_dev_step`` given ``group_state``), on every step path above and together with clipping and the EMA.  Each group's
 ``{lr, wd}`` is device state like the step: a scheduler step rewrites it from the host before the next replay, so the
 captured graph stays valid.  ``backbone_lr_mult != 1`` asks for pretrained weights (``pretrained``, else the model's
 ``backbone_pretrained`` mark that ``models.load_pretrained_backbone`` leaves).  ``lrs`` gives every group's lr by name.

@@ -15,13 +15,36 @@ def flat_adam_step(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.T
     load().flat_adam(p, g, m, v, lr, beta1, beta2, eps, weight_decay, lr / bc1, 1.0 / math.sqrt(bc2), grad_scale)
 
 
-def flat_adam_dev_step(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, state: torch.Tensor, *,
-                       beta1: float, beta2: float, eps: float, weight_decay: float, grad_scale: float = 1.0):
-    """Same update with {step, lr} read from the device tensor ``state`` (hipGraph-replayable)."""
-    load().flat_adam_dev(p, g, m, v, state, beta1, beta2, eps, weight_decay, grad_scale)
-
-
 CLIP_STATE_SLOTS = 8   # {norm, coef, ok, skipped steps, clipped steps, consecutive skipped steps, 0, 0}
+EMA_STATE_SLOTS = 4    # {omd_t used by the last applied update, t of that update, 0, 0}
+CHUNK = 64             # floats per chunk_group entry: parallel.flat.ALIGN, so a chunk lies inside one parameter
+MAX_GROUPS = 16
+GROUP_STATE_SLOTS = 4  # {lr, weight_decay, 0, 0} per group
+
+
+def flat_adam_dev_step(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, state: torch.Tensor, *,
+                       ema: torch.Tensor = None, ema_state: torch.Tensor = None, clip_state: torch.Tensor = None,
+                       group_state: torch.Tensor = None, chunk_group: torch.Tensor = None, beta1: float, beta2: float,
+                       eps: float, weight_decay: float = 0.0, grad_scale: float = 1.0, one_minus_decay: float = 1.0,
+                       warmup: bool = True):
+    """The same update with {step, lr} read from the device tensor ``state`` (hipGraph-replayable), in one launch of
+    one kernel template; the optional tensors select the form and every combination of them is allowed.
+
+    * ``clip_state`` fp32[8] (``grad_norm_clip_``'s verdict): untouched buffers when ok == 0,
+      ``g = (g * grad_scale) * coef`` otherwise, and the Adam step ``t`` is ``state[0]`` minus the skipped steps.
+    * ``ema`` and ``ema_state`` fp32[4], together: the launch also carries the exponential moving average of the
+      weights, ``ema += omd_t * (p_new - ema)`` with ``omd_t = max(one_minus_decay, 9 / (10 + t))`` under ``warmup``
+      (the decay ``min(decay, (1 + t) / (10 + t))``) and ``one_minus_decay`` without, ``t`` being the Adam step of this
+      call as the device sees it.  ``ema_state`` receives ``{omd_t, t, 0, 0}``; a skipped step touches neither.
+    * ``group_state`` fp32[G, 4] = ``{lr_g, wd_g, 0, 0}`` (``G <= 16``) and ``chunk_group`` uint8[n / 64], together:
+      ``lr`` and ``weight_decay`` per parameter group, ``chunk_group`` naming the group of each 64-float chunk;
+      ``state[1]`` (the ungrouped lr) and ``weight_decay`` are not read.
+
+    Every form runs the same per-element code on the same operands, so ``p, m, v`` of an applied step do not depend
+    on whether the average is carried, a verdict with ``coef == 1`` equals no verdict, and the elements of group ``g``
+    come out as the ungrouped form leaves them over the whole buffer with ``(lr_g, wd_g)``, bit for bit."""
+    load().flat_adam_dev(p, g, m, v, state, ema, ema_state, clip_state, group_state, chunk_group, beta1, beta2, eps,
+                         weight_decay, grad_scale, float(one_minus_decay), bool(warmup))
 
 
 def gradnorm_partials(n: int) -> int:
@@ -44,30 +67,19 @@ def grad_norm_clip_(grad: torch.Tensor, clip_state: torch.Tensor, partials: torc
 def flat_adam_clip_dev_step(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, state: torch.Tensor,
                             clip_state: torch.Tensor, *, beta1: float, beta2: float, eps: float, weight_decay: float,
                             grad_scale: float = 1.0):
-    """``flat_adam_dev_step`` under ``clip_state``: untouched buffers when ok == 0, ``g = (g * grad_scale) * coef``
-    otherwise, and the Adam step is ``state[0]`` minus the skipped steps."""
-    load().flat_adam_clip_dev(p, g, m, v, state, clip_state, beta1, beta2, eps, weight_decay, grad_scale)
-
-
-EMA_STATE_SLOTS = 4    # {omd_t used by the last applied update, t of that update, 0, 0}
+    """``flat_adam_dev_step`` under ``clip_state``."""
+    flat_adam_dev_step(p, g, m, v, state, clip_state=clip_state, beta1=beta1, beta2=beta2, eps=eps,
+                       weight_decay=weight_decay, grad_scale=grad_scale)
 
 
 def flat_adam_ema_dev_step(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, ema: torch.Tensor,
                            state: torch.Tensor, ema_state: torch.Tensor, clip_state: torch.Tensor = None, *,
                            beta1: float, beta2: float, eps: float, weight_decay: float, grad_scale: float = 1.0,
                            one_minus_decay: float, warmup: bool = True):
-    """``flat_adam_dev_step`` (``clip_state=None``) or ``flat_adam_clip_dev_step`` -- ``p, m, v`` come out bit for bit
-    the same -- that also carries the exponential moving average of the weights in the same launch:
-    ``ema += omd_t * (p_new - ema)`` with ``omd_t = max(one_minus_decay, 9 / (10 + t))`` under warm-up (the decay
-    ``min(decay, (1 + t) / (10 + t))``) and ``one_minus_decay`` without, ``t`` being the Adam step of this call as
-    the device sees it.  ``ema_state`` fp32[4] receives ``{omd_t, t, 0, 0}``; a skipped step touches neither."""
-    load().flat_adam_ema_dev(p, g, m, v, ema, state, ema_state, clip_state, beta1, beta2, eps, weight_decay,
-                             grad_scale, float(one_minus_decay), bool(warmup))
-
-
-CHUNK = 64             # floats per chunk_group entry: parallel.flat.ALIGN, so a chunk lies inside one parameter
-MAX_GROUPS = 16
-GROUP_STATE_SLOTS = 4  # {lr, weight_decay, 0, 0} per group
+    """``flat_adam_dev_step`` with the average of the weights, with or without ``clip_state``."""
+    flat_adam_dev_step(p, g, m, v, state, ema=ema, ema_state=ema_state, clip_state=clip_state, beta1=beta1,
+                       beta2=beta2, eps=eps, weight_decay=weight_decay, grad_scale=grad_scale,
+                       one_minus_decay=one_minus_decay, warmup=warmup)
 
 
 def flat_adam_groups_dev_step(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, state: torch.Tensor,
@@ -75,14 +87,10 @@ def flat_adam_groups_dev_step(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor,
                               ema_state: torch.Tensor = None, clip_state: torch.Tensor = None, beta1: float,
                               beta2: float, eps: float, grad_scale: float = 1.0, one_minus_decay: float = 1.0,
                               warmup: bool = True):
-    """The device-state update with ``lr`` and ``weight_decay`` per parameter group, in one launch: ``chunk_group``
-    uint8[n / 64] names the group of each 64-float chunk and ``group_state`` fp32[G, 4] holds ``{lr_g, wd_g, 0, 0}``
-    (``G <= 16``).  The form follows the arguments like the ungrouped ops: ``flat_adam_dev_step`` (neither),
-    ``flat_adam_clip_dev_step`` (``clip_state``), ``flat_adam_ema_dev_step`` (``ema`` and ``ema_state``, with or
-    without ``clip_state``).  The elements of group ``g`` come out bit for bit as that op leaves them when it runs
-    over the whole buffer with ``(lr_g, wd_g)``; ``state[1]`` (the ungrouped lr) is not read."""
-    load().flat_adam_groups_dev(p, g, m, v, ema, state, group_state, chunk_group, ema_state, clip_state, beta1, beta2,
-                                eps, grad_scale, float(one_minus_decay), bool(warmup))
+    """``flat_adam_dev_step`` with ``lr`` and ``weight_decay`` per parameter group, in any of its forms."""
+    flat_adam_dev_step(p, g, m, v, state, ema=ema, ema_state=ema_state, clip_state=clip_state,
+                       group_state=group_state, chunk_group=chunk_group, beta1=beta1, beta2=beta2, eps=eps,
+                       grad_scale=grad_scale, one_minus_decay=one_minus_decay, warmup=warmup)
 
 
 SCHED_KINDS = ("constant", "linear", "cosine", "rsqrt")   # the kernel's kind argument is the index

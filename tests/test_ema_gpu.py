@@ -456,18 +456,21 @@ def test_defaults_stay_on_the_old_path():
     cfg = _cfg()
     eng = _engine(cfg)
     assert eng.optimizer.ema is None and eng.optimizer.ema_state is None and eng.optimizer.ema_decay_now is None
-    with mock.patch.object(ext, "flat_adam_dev", wraps=ext.flat_adam_dev) as old, \
-            mock.patch.object(ext, "flat_adam_ema_dev", wraps=ext.flat_adam_ema_dev) as new:
+    # the one binding carries every form: its optional tensors (ema, ema_state, clip_state, group_state, chunk_group:
+    # positions 5 to 9) select the kernel, and the old path is the call in which all of them are absent
+    with mock.patch.object(ext, "flat_adam_dev", wraps=ext.flat_adam_dev) as adam_dev:
         for b in _batches(cfg, 2):
             eng.train_step(b)
         torch.cuda.synchronize()
-    assert old.call_count == 2 and new.call_count == 0
+    assert adam_dev.call_count == 2
+    assert all(len(c.args) == 17 and all(a is None for a in c.args[5:10]) for c in adam_dev.call_args_list)
     ck = build_checkpoint(eng.model, eng.optimizer, eng.scheduler, ema=ema_entry(eng.optimizer))
     assert "ema" not in ck
-    # and with the option on the new binding is the only Adam launch
+    # and with the option on the EMA form is the only Adam launch
     on = _engine(cfg, ema_decay=0.999)
-    with mock.patch.object(ext, "flat_adam_dev", wraps=ext.flat_adam_dev) as old, \
-            mock.patch.object(ext, "flat_adam_ema_dev", wraps=ext.flat_adam_ema_dev) as new:
+    with mock.patch.object(ext, "flat_adam_dev", wraps=ext.flat_adam_dev) as adam_dev:
         on.train_step(_batches(cfg, 1)[0])
         torch.cuda.synchronize()
-    assert old.call_count == 0 and new.call_count == 1
+    assert adam_dev.call_count == 1
+    args = adam_dev.call_args.args
+    assert args[5] is on.optimizer.ema and args[6] is on.optimizer.ema_state and all(a is None for a in args[7:10])

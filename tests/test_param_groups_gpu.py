@@ -1,4 +1,4 @@
-"""Parameter groups inside the fused Adam launch, on the GPU: flat_adam_groups_kernel<CLIP, EMA> against the existing
+"""Parameter groups inside the fused Adam launch, on the GPU: flat_adam_kernel's GROUPS forms against the existing
 ungrouped kernels group by group (bitwise), across steps and a skipped step, with equal groups, against an fp64
 reference, the binding's refusals, and the engine's eager / one-graph steps, defaults and resume.
 
@@ -454,12 +454,13 @@ def test_default_engine_stays_on_the_ungrouped_kernel():
     opt = eng.optimizer
     assert len(opt.param_groups) == 1 and opt.chunk_group is None and opt.group_state is None
     assert "name" not in opt.param_groups[0] and eng.lrs == {"all": LR}
-    with mock.patch.object(adam, "flat_adam_dev_step", wraps=adam.flat_adam_dev_step) as old, \
-            mock.patch.object(adam, "flat_adam_groups_dev_step", wraps=adam.flat_adam_groups_dev_step) as new:
+    # the one op carries every form: group_state and chunk_group select the grouped kernel, None the ungrouped one
+    with mock.patch.object(adam, "flat_adam_dev_step", wraps=adam.flat_adam_dev_step) as step:
         for b in batches:
             eng.train_step(b)
         torch.cuda.synchronize()
-    assert old.call_count == 3 and new.call_count == 0
+    assert step.call_count == 3
+    assert all(c.kwargs["group_state"] is None and c.kwargs["chunk_group"] is None for c in step.call_args_list)
     # the same engine on the parent's optimizer step
     ref = _engine(cfg, grouped=False)
     ref.optimizer.step = lambda closure=None, grad_scale=1.0: _parent_step(ref.optimizer, grad_scale)
@@ -469,13 +470,14 @@ def test_default_engine_stays_on_the_ungrouped_kernel():
     assert torch.equal(eng.flat.data, ref.flat.data)
     assert torch.equal(opt.exp_avg, ref.optimizer.exp_avg) and torch.equal(opt.exp_avg_sq, ref.optimizer.exp_avg_sq)
     assert torch.equal(opt.dev_state, ref.optimizer.dev_state)
-    # with groups the grouped binding is the only Adam launch
+    # with groups the grouped form is the only Adam launch
     on = _engine(cfg)
-    with mock.patch.object(adam, "flat_adam_dev_step", wraps=adam.flat_adam_dev_step) as old, \
-            mock.patch.object(adam, "flat_adam_groups_dev_step", wraps=adam.flat_adam_groups_dev_step) as new:
+    with mock.patch.object(adam, "flat_adam_dev_step", wraps=adam.flat_adam_dev_step) as step:
         on.train_step(batches[0])
         torch.cuda.synchronize()
-    assert old.call_count == 0 and new.call_count == 1
+    assert step.call_count == 1
+    kw = step.call_args.kwargs
+    assert kw["group_state"] is on.optimizer.group_state and kw["chunk_group"] is on.optimizer.chunk_group
 
 
 def test_resume_restores_the_groups(tmp_path):

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Cost of the per-element group lookup in the fused Adam (csrc/kernels/adam.hip, flat_adam_groups_kernel) on the GPU.
+"""Cost of the per-element group lookup in the fused Adam (csrc/kernels/adam.hip, the GROUPS forms) on the GPU.
 
   python tools/bench_adam_groups.py kernels   # at the full model's flat size, in one process: the ungrouped kernel and
                                               # the grouped one over the real model's four-group layout, in the plain

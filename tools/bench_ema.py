@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Cost of the exponential moving average of the weights (csrc/kernels/adam.hip, flat_adam_ema_kernel) on the GPU.
+"""Cost of the exponential moving average of the weights (csrc/kernels/adam.hip, the EMA forms) on the GPU.
 
   python tools/bench_ema.py kernels      # (a) at the full model's size, in one process: the unchanged flat_adam_dev,
                                          #     flat_adam_dev + torch's lerp_ (the two-launch alternative), and the

@@ -221,8 +221,16 @@ int main(int argc, char** argv) {
         EXPECT(rt1_grad_clip_finalize(nullptr, 0, 1.f, 1.f, 1, nullptr, nullptr) != 0);
         EXPECT(rt1_grad_clip_finalize(nullptr, cap + 1, 1.f, 1.f, 1, nullptr, nullptr) != 0);
         EXPECT(rt1_buffer_guard(nullptr, nullptr, 0, nullptr, nullptr) != 0);
-        EXPECT(rt1_flat_adam_clip_dev(nullptr, nullptr, nullptr, nullptr, 64, nullptr, nullptr, 0.9f, 0.999f, 1e-8f,
-                                      0.f, 1.f, nullptr) != 0);
+        EXPECT(rt1_flat_adam_dev(nullptr, nullptr, nullptr, nullptr, 64, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                 nullptr, 0, 0.9f, 0.999f, 1e-8f, 0.f, 1.f, 1.f, 0, nullptr) != 0);
+        // with a state: groups given and n % 64 != 0, and an EMA buffer without ema_state (the pointers are compared
+        // with null and never read: every case returns before the launch)
+        float buf[8] = {0};
+        const uint8_t table[2] = {0, 0};
+        EXPECT(rt1_flat_adam_dev(buf, buf, buf, buf, 100, buf, nullptr, nullptr, nullptr, buf, table, 2, 0.9f, 0.999f,
+                                 1e-8f, 0.f, 1.f, 1.f, 0, nullptr) == (int)hipErrorInvalidValue);
+        EXPECT(rt1_flat_adam_dev(buf, buf, buf, buf, 64, buf, nullptr, buf, nullptr, nullptr, nullptr, 0, 0.9f, 0.999f,
+                                 1e-8f, 0.f, 1.f, 1.f, 0, nullptr) == (int)hipErrorInvalidValue);
     }
     std::printf("host checks: %ld shape cases, %d failures\n", checked, failures);
     return failures == 0 ? 0 : 1;
