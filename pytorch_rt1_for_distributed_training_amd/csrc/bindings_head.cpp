@@ -398,6 +398,37 @@ std::vector<at::Tensor> se_bwd(at::Tensor red, at::Tensor gate, at::Tensor h, at
     return {dw2, db2, dw1, db1, rb, sdz, sdzx, mdz, mdzx};
 }
 
+// Test-only: the per-frame half of se_bwd on its own, so that the tests can hold the weight sums to the dh that
+// reached memory.  dsum, gate [N, C], h [N, S] -> {dh [N, S], rb [N, C]}
+std::vector<at::Tensor> se_bwd_frame(at::Tensor dsum, at::Tensor gate, at::Tensor h, double inv_hw, at::Tensor w1,
+                                     at::Tensor w2) {
+    check_dev(dsum, "dsum", at::kFloat); check_dev(gate, "gate", at::kFloat); check_dev(h, "h", at::kFloat);
+    check_dev(w1, "w1", at::kFloat); check_dev(w2, "w2", at::kFloat);
+    TORCH_CHECK(gate.dim() == 2 && dsum.sizes() == gate.sizes(), "se_bwd_frame: dsum / gate must be [N, C]");
+    const int64_t N = gate.size(0), C = gate.size(1);
+    TORCH_CHECK(h.dim() == 2 && h.size(0) == N, "se_bwd_frame: h must be [N, S]");
+    const int64_t S = h.size(1);
+    TORCH_CHECK(w1.numel() == S * C && w2.numel() == C * S, "se_bwd_frame: weight shapes");
+    TORCH_CHECK(C % 4 == 0 && S <= 128, "se_bwd_frame: C % 4 == 0 and S <= 128 required");
+    auto f = gate.options();
+    auto rb = at::empty_like(gate);
+    auto dh = at::empty({N, S}, f);
+    auto part = at::empty({(int64_t)rt1_se_part_size((int)N, (int)C, (int)S)}, f);
+    check_launch(rt1_se_bwd_frame(dsum.data_ptr<float>(), gate.data_ptr<float>(), h.data_ptr<float>(), (float)inv_hw,
+                                  (int)N, (int)C, (int)S, w1.data_ptr<float>(), w2.data_ptr<float>(),
+                                  part.data_ptr<float>(), dh.data_ptr<float>(), rb.data_ptr<float>(), cur_stream()),
+                 "se_bwd_frame");
+    return {dh, rb};
+}
+
+// Test-only: rt1_se_plan's ten figures for a shape (K slices, channels per slice, se_rowmat frames fwd / bwd, its LDS
+// bytes fwd / bwd, frame slices, frames per slice, se_wsum_fin workgroups, whether the LDS limit is raised)
+std::vector<int64_t> se_plan(int64_t N, int64_t C, int64_t S) {
+    int o[10];
+    TORCH_CHECK(rt1_se_plan((int)N, (int)C, (int)S, o) == 0, "se_plan: unsupported shape");
+    return std::vector<int64_t>(o, o + 10);
+}
+
 std::vector<at::Tensor> se_bwd_bnsum(at::Tensor red, at::Tensor gate, at::Tensor rbraw, double inv_hw, double count) {
     check_dev(red, "red", at::kFloat);
     check_dev(gate, "gate", at::kFloat);
@@ -424,6 +455,8 @@ void register_head(py::module_& m) {
     m.def("se_fwd", &se_fwd);
     m.def("se_bwd", &se_bwd);
     m.def("se_bwd_bnsum", &se_bwd_bnsum);
+    m.def("se_bwd_frame", &se_bwd_frame);
+    m.def("se_plan", &se_plan);
     m.def("embed_fwd", &embed_fwd);
     m.def("pw_tall_supported", &pw_tall_supported);
     m.def("pw_tall", &pw_tall, py::arg("A"), py::arg("W"), py::arg("scale") = py::none(), py::arg("shift") = py::none(),

@@ -557,18 +557,42 @@ int rd_splits(int N, int C, int S) {
 #ifndef SE_RM_WIDE_WG_BWD
 #define SE_RM_WIDE_WG_BWD 300
 #endif
-template <bool BWD>
-void launch_rowmat(const float* part, int KS, const float* b1, const float* hin, float* yout, const float* V,
-                   const float* b2, float inv_hw, int N, int C, int S, float* out, hipStream_t st) {
+// dynamic LDS of se_rowmat: the Y rows [FT][S] and the V tile (fwd [RM_CT][S | 1], bwd [S][RM_CT])
+constexpr size_t rm_lds_bytes(bool bwd, int ft, int S) {
+    return (size_t)(ft * S + RM_CT * (bwd ? S : rm_fwd_stride(S))) * sizeof(float);
+}
+constexpr int SE_S_MAX = 128;                    // NVB of se_rowmat holds the V tile up to here
+constexpr size_t SE_LDS_DEFAULT = 64 * 1024;     // the largest dynamic request a launch gets without the attribute
+
+int rm_frames(bool bwd, int N, int C) {
     const int ct = (C + RM_CT - 1) / RM_CT;
-    if (((N + 31) / 32) * ct >= (BWD ? SE_RM_WIDE_WG_BWD : SE_RM_WIDE_WG_FWD))
-        hipLaunchKernelGGL((se_rowmat_kernel<BWD, 32>), dim3((N + 31) / 32, ct), dim3(SE_BLOCK),
-                           (size_t)(32 * S + RM_CT * (BWD ? S : rm_fwd_stride(S))) * sizeof(float), st, part, KS, b1, hin, yout, V, b2, inv_hw, N,
-                           C, S, out);
-    else
-        hipLaunchKernelGGL((se_rowmat_kernel<BWD, 16>), dim3((N + 15) / 16, ct), dim3(SE_BLOCK),
-                           (size_t)(16 * S + RM_CT * (BWD ? S : rm_fwd_stride(S))) * sizeof(float), st, part, KS, b1, hin, yout, V, b2, inv_hw, N,
-                           C, S, out);
+    return ((N + 31) / 32) * ct >= (bwd ? SE_RM_WIDE_WG_BWD : SE_RM_WIDE_WG_FWD) ? 32 : 16;
+}
+
+// S in (96, 128] asks for more than 64 KB (forward: from S = 102 on 32-frame tiles, S = 114 on 16-frame ones, 82,432 B
+// at S = 128): such a launch needs the kernel's limit raised first, once per instantiation, to what S_MAX asks for.  The
+// model's widest S (96: 61,952 B) never gets here, so its launches are unchanged.
+template <bool BWD, int FT>
+int launch_rowmat_ft(const float* part, int KS, const float* b1, const float* hin, float* yout, const float* V,
+                     const float* b2, float inv_hw, int N, int C, int S, float* out, hipStream_t st) {
+    auto kern = se_rowmat_kernel<BWD, FT>;
+    const size_t lds = rm_lds_bytes(BWD, FT, S);
+    if (lds > SE_LDS_DEFAULT) {
+        static const hipError_t attr = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                           (int)rm_lds_bytes(BWD, FT, SE_S_MAX));
+        if (attr != hipSuccess) return (int)attr;
+    }
+    hipLaunchKernelGGL(kern, dim3((N + FT - 1) / FT, (C + RM_CT - 1) / RM_CT), dim3(SE_BLOCK), lds, st, part, KS, b1, hin,
+                       yout, V, b2, inv_hw, N, C, S, out);
+    return (int)hipGetLastError();
+}
+
+template <bool BWD>
+int launch_rowmat(const float* part, int KS, const float* b1, const float* hin, float* yout, const float* V,
+                  const float* b2, float inv_hw, int N, int C, int S, float* out, hipStream_t st) {
+    if (rm_frames(BWD, N, C) == 32)
+        return launch_rowmat_ft<BWD, 32>(part, KS, b1, hin, yout, V, b2, inv_hw, N, C, S, out, st);
+    return launch_rowmat_ft<BWD, 16>(part, KS, b1, hin, yout, V, b2, inv_hw, N, C, S, out, st);
 }
 
 // frame slices of se_wsum_part: WS_NS, more (up to WS_NS_MAX) where the (channel x unit) tiles alone give few
@@ -624,30 +648,52 @@ int rt1_se_bwd_bnsum(const float* red, const float* gate, const float* rbraw, fl
 
 int rt1_se_part_size(int N, int C, int S) { return rd_splits(N, C, S) * N * S; }
 
+// The launch plan of the four SE kernels for one shape, as the entries below form it (tests assert the route they
+// mean to walk; the host checks hold the LDS request to the limit): out[0] K slices of se_rowdot, out[1] channels per
+// slice, out[2] / out[3] frames per se_rowmat tile fwd / bwd, out[4] / out[5] its dynamic LDS bytes fwd / bwd,
+// out[6] frame slices of se_wsum_part that run, out[7] frames per slice, out[8] workgroups of se_wsum_fin,
+// out[9] 1 where a se_rowmat launch of this shape raises the kernel's dynamic LDS limit first.
+int rt1_se_plan(int N, int C, int S, int* out) {
+    if (N <= 0 || C <= 0 || S <= 0 || S > SE_S_MAX || C % 4 || !out) return (int)hipErrorInvalidValue;
+    const int ks = rd_splits(N, C, S);
+    const int kslice = ((C + ks - 1) / ks + RD_KC - 1) / RD_KC * RD_KC;
+    out[0] = (C + kslice - 1) / kslice;
+    out[1] = kslice;
+    out[2] = rm_frames(false, N, C);
+    out[3] = rm_frames(true, N, C);
+    out[4] = (int)rm_lds_bytes(false, out[2], S);
+    out[5] = (int)rm_lds_bytes(true, out[3], S);
+    const int ns = ws_splits(N, C, S);
+    out[7] = (N + ns - 1) / ns;
+    out[6] = (N + out[7] - 1) / out[7];
+    const int64_t total = 2 * (int64_t)C * S + C + S;
+    out[8] = (int)std::min<int64_t>(1024, (total + SE_BLOCK - 1) / SE_BLOCK);
+    out[9] = (size_t)out[4] > SE_LDS_DEFAULT || (size_t)out[5] > SE_LDS_DEFAULT;
+    return 0;
+}
+
 // pool_sum [N, C] (frame_pool) -> h = fc1 pre-activation [N, S], gate [N, C]; part: rt1_se_part_size floats
 int rt1_se_fwd(const float* pool_sum, float inv_hw, int N, int C, int S, const float* w1, const float* b1,
                const float* w2, const float* b2, float* part, float* h, float* gate, hipStream_t st) {
-    if (N <= 0 || C <= 0 || S <= 0 || S > 128 || C % 4) return (int)hipErrorInvalidValue;
+    if (N <= 0 || C <= 0 || S <= 0 || S > SE_S_MAX || C % 4) return (int)hipErrorInvalidValue;
     const int ks = rd_splits(N, C, S);
     const int kslice = ((C + ks - 1) / ks + RD_KC - 1) / RD_KC * RD_KC;
     const int ksn = (C + kslice - 1) / kslice;
     hipLaunchKernelGGL(se_rowdot_kernel<false>, dim3((N + RD_FT - 1) / RD_FT, (S + RD_JT - 1) / RD_JT, ksn),
                        dim3(SE_BLOCK), 0, st, pool_sum, nullptr, w1, N, C, S, kslice, part);
-    launch_rowmat<false>(part, ksn, b1, nullptr, h, w2, b2, inv_hw, N, C, S, gate, st);
-    return (int)hipGetLastError();
+    return launch_rowmat<false>(part, ksn, b1, nullptr, h, w2, b2, inv_hw, N, C, S, gate, st);
 }
 
 // dsum = red row 0 [N, C], gate [N, C], h [N, S] -> dh [N, S], rb [N, C]
 int rt1_se_bwd_frame(const float* dsum, const float* gate, const float* h, float inv_hw, int N, int C, int S,
                      const float* w1, const float* w2, float* part, float* dh, float* rb, hipStream_t st) {
-    if (N <= 0 || C <= 0 || S <= 0 || S > 128 || C % 4) return (int)hipErrorInvalidValue;
+    if (N <= 0 || C <= 0 || S <= 0 || S > SE_S_MAX || C % 4) return (int)hipErrorInvalidValue;
     const int ks = rd_splits(N, C, S);
     const int kslice = ((C + ks - 1) / ks + RD_KC - 1) / RD_KC * RD_KC;
     const int ksn = (C + kslice - 1) / kslice;
     hipLaunchKernelGGL(se_rowdot_kernel<true>, dim3((N + RD_FT - 1) / RD_FT, (S + RD_JT - 1) / RD_JT, ksn),
                        dim3(SE_BLOCK), 0, st, dsum, gate, w2, N, C, S, kslice, part);
-    launch_rowmat<true>(part, ksn, nullptr, h, dh, w1, nullptr, inv_hw, N, C, S, rb, st);
-    return (int)hipGetLastError();
+    return launch_rowmat<true>(part, ksn, nullptr, h, dh, w1, nullptr, inv_hw, N, C, S, rb, st);
 }
 
 // workspace floats for rt1_se_bwd_wsum: 2 * NS * C * S floats + (3 * NS * C + NS * S) doubles

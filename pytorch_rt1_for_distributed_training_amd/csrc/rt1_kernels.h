@@ -232,6 +232,7 @@ int rt1_drop_bwd(const float* dout, int T, float p, uint32_t seed, const uint32_
 
 // se.hip (SE + BN2 backward glue of an MBConv block)
 int rt1_se_part_size(int N, int C, int S);
+int rt1_se_plan(int N, int C, int S, int* out);   // out[10]: the launch plan of the shape (see se.hip)
 int rt1_se_fwd(const float* pool_sum, float inv_hw, int N, int C, int S, const float* w1, const float* b1,
                const float* w2, const float* b2, float* part, float* h, float* gate, hipStream_t st);
 int rt1_se_bwd_frame(const float* dsum, const float* gate, const float* h, float inv_hw, int N, int C, int S,

@@ -7,7 +7,7 @@ OUT="$ROOT/build/asan"
 mkdir -p "$OUT"
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 SAN="-Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined -Xarch_host -fno-omit-frame-pointer"
-SRCS="dw_plan dw_fwd dw_bwd_s1 dw_bwd_s2 pwgemm pwtall pwbwd block stem head tokenlearner transformer gradnorm adam"
+SRCS="dw_plan dw_fwd dw_bwd_s1 dw_bwd_s2 pwgemm pwtall pwbwd block stem se head tokenlearner transformer gradnorm adam"
 pids=()
 objs=("$OUT/host_checks.o")
 for s in $SRCS; do

@@ -181,6 +181,46 @@ int main(int argc, char** argv) {
     for (int p : {1, 64, 100, 120, 225, 256, 257, 1000}) rt1_tl_supported(p, 512, 64, 8);
     EXPECT(!rt1_tl_supported(257, 512, 64, 8));
     for (int v : {2, 128, 256, 512, 1024, 4096}) rt1_head_ce_supported(v, 512);
+    // SE MLP: S > 128, C % 4 != 0 and empty shapes are refused before any launch by both entries and the plan; for
+    // every admitted S the se_rowmat request fits the 160 KB of a CU, and whatever passes 64 KB (from S = 102 on
+    // 32-frame forward tiles, S = 114 on 16-frame ones) is flagged to raise the kernel's limit first
+    {
+        const int bad = (int)hipErrorInvalidValue;
+        int o[10];
+        for (int s : {0, 129, 130, 1 << 20}) {
+            EXPECT(rt1_se_fwd(nullptr, 1.f, 16, 128, s, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                              nullptr) == bad);
+            EXPECT(rt1_se_bwd_frame(nullptr, nullptr, nullptr, 1.f, 16, 128, s, nullptr, nullptr, nullptr, nullptr,
+                                    nullptr, nullptr) == bad);
+            EXPECT(rt1_se_plan(16, 128, s, o) == bad);
+        }
+        EXPECT(rt1_se_fwd(nullptr, 1.f, 16, 130, 8, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                          nullptr) == bad);
+        EXPECT(rt1_se_bwd_frame(nullptr, nullptr, nullptr, 1.f, 0, 128, 8, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                nullptr) == bad);
+        EXPECT(rt1_se_plan(16, 128, 8, nullptr) == bad);
+        for (int n : {1, 16, 352, 353, 512, 513, 768, 1536})
+            for (int c : {24, 128, 1392, 2304})
+                for (int s = 1; s <= 128; ++s) {
+                    EXPECT(rt1_se_plan(n, c, s, o) == 0);
+                    for (int b = 0; b < 2; ++b) {
+                        const int ft = o[2 + b], lds = o[4 + b];
+                        EXPECT(ft == 16 || ft == 32);
+                        EXPECT(lds == (ft * s + 128 * (b ? s : (s | 1))) * 4 && lds <= 160 * 1024);
+                    }
+                    EXPECT(o[9] == (o[4] > 64 * 1024 || o[5] > 64 * 1024));
+                    if (s <= 101) EXPECT(o[9] == 0);       // the model stops at 96
+                    if (s >= 114) EXPECT(o[9] == 1);
+                    if (o[2] == 32) EXPECT(o[9] == (s >= 102));
+                    EXPECT(o[0] >= 1 && o[0] <= (c + 63) / 64 && o[1] % 64 == 0 && o[0] * o[1] >= c);
+                    EXPECT(o[6] >= 1 && o[6] <= 32 && o[6] * o[7] >= n && (o[6] - 1) * o[7] < n);
+                    EXPECT(o[8] >= 1 && o[8] <= 1024);
+                    EXPECT(rt1_se_part_size(n, c, s) >= o[0] * n * s);
+                    ++checked;
+                }
+        EXPECT(rt1_se_plan(16, 128, 128, o) == 0 && o[4] == 82432 - 16 * 128 * 4 && o[9] == 1);
+        EXPECT(rt1_se_plan(768, 2304, 128, o) == 0 && o[2] == 32 && o[4] == 82432);
+    }
     // the regularised head refuses label smoothing outside [0, 1), a negative or non-finite z-loss and an unknown
     // vocabulary, and the hit counter a slot count outside [1, 32] or no rows, all before any launch
     {
