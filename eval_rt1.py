@@ -3,6 +3,7 @@
   python eval_rt1.py --ckpt exp/ckpt/exp_rt1/last.ckpt --env toy --episodes 10
   python eval_rt1.py --ckpt ... --env sim --reward block2block   # in-tree Language-Table board (sim/)
   python eval_rt1.py --ckpt ... --env language_table     # needs pybullet + language_table + a USE encoder
+  python eval_rt1.py --ckpt ... --saliency               # + <episode>_saliency.gif: what the action tokens looked at
 
 Protocol kept from the reference: BlockToBlock reward, 10 episodes, at most 80
 (+1) policy steps, 456x256 central crop with factor 0.95, 6-frame history, the
@@ -35,7 +36,15 @@ def main(argv=None):
     ap.add_argument("--no_video", action="store_true")
     ap.add_argument("--ema", action="store_true",
                     help="evaluate the checkpoint's averaged weights (written when training ran with --ema_decay)")
+    ap.add_argument("--saliency", action="store_true",
+                    help="write a second GIF per episode (..._saliency.gif): the frames the policy read, blended with "
+                         "the image regions its action tokens attended to (last layer, through the TokenLearner maps)")
+    ap.add_argument("--no_token_learner", action="store_true", help="the checkpoint was trained without TokenLearner")
     a = ap.parse_args(argv)
+    if a.saliency and a.no_token_learner:
+        ap.error("--saliency needs TokenLearner: its spatial maps are what the attention is projected on")
+    if a.saliency and a.no_video:
+        ap.error("--saliency writes GIFs: drop --no_video")
 
     import torch
     from pytorch_rt1_for_distributed_training_amd.config import RT1Config
@@ -43,7 +52,8 @@ def main(argv=None):
                                                                make_language_table_env, make_sim_env)
     torch.manual_seed(a.seed)
     device = a.device or ("cuda" if torch.cuda.is_available() else "cpu")
-    cfg = RT1Config(height=a.height, width=a.width, seq_len=a.seq_len, num_layers=a.num_layers)
+    cfg = RT1Config(height=a.height, width=a.width, seq_len=a.seq_len, num_layers=a.num_layers,
+                    use_token_learner=not a.no_token_learner, return_attention_scores=a.saliency)
     policy = RT1Policy.from_checkpoint(a.ckpt, cfg, device=device, use_ema=a.ema)
     if a.env == "sim":
         env = make_sim_env(a.reward, a.block_mode, seed=a.seed, reject_unsolvable=not a.no_reject)
@@ -53,7 +63,7 @@ def main(argv=None):
         env = make_language_table_env(seed=a.seed)
     res = evaluate(policy, env, episodes=a.episodes, max_episode_steps=a.max_episode_steps, name=a.reward,
                    crop=CentralCropResize(a.width, a.height, a.random_crop_factor), history_length=a.seq_len,
-                   video_dir=None if a.no_video else f"{a.workdir}/videos")
+                   video_dir=None if a.no_video else f"{a.workdir}/videos", saliency=a.saliency)
     print(json.dumps(res))
     return 0
 

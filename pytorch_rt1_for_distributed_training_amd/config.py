@@ -30,6 +30,7 @@ class RT1Config:
     feed_forward_size: int = 512     # d_model
     dropout_rate: float = 0.1
     max_seq_len: int = 256           # learned position table (transformer.py:156)
+    return_attention_scores: bool = False   # keep every layer's [B, H, S, S] probabilities and the TokenLearner maps
     # image tokenizer
     use_token_learner: bool = True
     num_image_tokens: int = 8

@@ -203,6 +203,38 @@ at::Tensor attn_bwd_long(at::Tensor qkv, at::Tensor out, at::Tensor dout, at::Te
     return dqkv;
 }
 
+// the forward's dropped attention probabilities, fp32 [B, H, S, S] (eager layout), from qkv and the lse that attn_fwd
+// stored; `out`, when given, is written in place (every element)
+at::Tensor attn_probs(at::Tensor qkv, at::Tensor lse, int64_t L, int64_t Kimg, double scale, double drop_p, int64_t seed,
+                      OptT seed_dev, OptT out) {
+    check_dev(qkv, "qkv", at::kBFloat16);
+    check_dev(lse, "lse", at::kFloat);
+    TORCH_CHECK(qkv.dim() == 5 && qkv.size(2) == 3, "attn_probs: qkv must be [B, S, 3, H, 128]");
+    TORCH_CHECK(qkv.size(4) == 128, "attn_probs: head dimension D = ", qkv.size(4), ", only D = 128 is supported");
+    const int64_t B = qkv.size(0), S = qkv.size(1), H = qkv.size(3);
+    TORCH_CHECK(S >= 1 && S <= 256, "attn_probs supports 1 <= S <= 256, got S = ", S);
+    TORCH_CHECK(B >= 1 && H >= 1 && B * H < ((int64_t)1 << 31), "attn_probs: bad batch / head count");
+    TORCH_CHECK(L > 0 && Kimg >= 0 && Kimg <= L, "attn_probs: bad token layout");
+    TORCH_CHECK(drop_p >= 0.0 && drop_p < 1.0, "attn_probs: drop_p must be in [0, 1), got ", drop_p);
+    TORCH_CHECK(lse.numel() == B * H * S, "attn_probs: lse must be [B, H, S] = [", B, ", ", H, ", ", S, "], got ",
+                lse.sizes());
+    TORCH_CHECK(lse.get_device() == qkv.get_device(), "attn_probs: lse and qkv are on different devices");
+    at::Tensor o;
+    if (out.has_value() && out->defined()) {
+        o = *out;
+        check_dev(o, "out", at::kFloat);
+        TORCH_CHECK(o.sizes() == at::IntArrayRef({B, H, S, S}), "attn_probs: out must be [B, H, S, S] = [", B, ", ", H,
+                    ", ", S, ", ", S, "], got ", o.sizes());
+        TORCH_CHECK(o.get_device() == qkv.get_device(), "attn_probs: out and qkv are on different devices");
+    } else {
+        o = at::empty({B, H, S, S}, lse.options());
+    }
+    check_launch(rt1_attn_probs(bp(qkv), lse.data_ptr<float>(), o.data_ptr<float>(), (int)B, (int)S, (int)H, (int)L,
+                                (int)Kimg, (float)scale, (float)drop_p, (uint32_t)seed, seed_ptr(seed_dev),
+                                cur_stream()), "attn_probs");
+    return o;
+}
+
 bool tl_supported(int64_t P, int64_t Cc, int64_t h1, int64_t t) {
     return rt1_tl_supported((int)P, (int)Cc, (int)h1, (int)t) != 0;
 }
@@ -474,6 +506,8 @@ void register_head(py::module_& m) {
     m.def("attn_bwd_long", &attn_bwd_long, py::arg("qkv"), py::arg("out"), py::arg("dout"), py::arg("lse"),
           py::arg("L"), py::arg("Kimg"), py::arg("scale"), py::arg("drop_p"), py::arg("seed"),
           py::arg("seed_dev") = py::none());
+    m.def("attn_probs", &attn_probs, py::arg("qkv"), py::arg("lse"), py::arg("L"), py::arg("Kimg"), py::arg("scale"),
+          py::arg("drop_p"), py::arg("seed"), py::arg("seed_dev") = py::none(), py::arg("out") = py::none());
 }
 
 }  // namespace rt1head

@@ -682,9 +682,88 @@ __global__ __launch_bounds__(256) void rt1_attn_bwd_dq_kernel(const bf16_t* __re
     }
 }
 
+// ------------------------------------------------------------------ attention probabilities (S <= 256)
+// The forward's dropped probabilities, which it never stores, as fp32 [B, H, S, S] from qkv and the saved log-sum-exp:
+//   out[b, h, i, j] = allowed(i, j) ? exp(scale q_i . k_j - lse[b, h, i]) keep(b, h, i, j) / (1 - p) : 0
+// in the backward kernels' order of operations (`sacc * scale - lrow`, then __expf), with this file's attn_allowed and
+// hash_uniform: the mask and the keep bits are the forward's by construction.  One wave per (batch, head, 16-query
+// row block); Q and K rows are MFMA operands as they lie in global memory (16 B per lane), so there is no LDS and no
+// barrier.  Key blocks above the causal diagonal cost no MFMA and are written as zeros: every element of out is
+// stored (no host memset), each store instruction covers 4 rows x 16 keys = 64 contiguous bytes per row (rows are 4 S
+// bytes, so only 4-byte aligned for odd S).  No atomics: bitwise repeatable.
+__global__ __launch_bounds__(256) void rt1_attn_probs_kernel(const bf16_t* __restrict__ qkv,
+                                                             const float* __restrict__ lse, float* __restrict__ out,
+                                                             int S, int H, int L, int Kimg, float scale, float drop_p,
+                                                             uint32_t salt, const uint32_t* __restrict__ seed_dev) {
+    const uint32_t seed = dev_seed(salt, seed_dev);
+    const int bh = blockIdx.x;
+    const int b = bh / H, h = bh % H;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lr = lane & 15, lg = lane >> 4;
+    const int nrb = (S + 15) / 16;
+    const int rb = blockIdx.y * 4 + wave;
+    if (rb >= nrb) return;                                     // no barrier below: a wave may leave alone
+    const int q0 = rb * 16;
+    const int64_t rs3 = 3LL * H * D;
+    const bf16_t* qbase = qkv + (int64_t)b * S * rs3 + (int64_t)h * D;
+    const bf16_t* kbase = qbase + (int64_t)H * D;
+    bf16x8 qf[D / 32];
+#pragma unroll
+    for (int ks = 0; ks < D / 32; ++ks) {
+        uint4 u = make_uint4(0, 0, 0, 0);
+        if (q0 + lr < S) u = *reinterpret_cast<const uint4*>(qbase + (int64_t)(q0 + lr) * rs3 + 32 * ks + 8 * lg);
+        qf[ks] = *reinterpret_cast<bf16x8*>(&u);
+    }
+    // C layout: [r] -> (i = q0 + 4 lg + r, j = kb * 16 + lr)
+    float lrow[4];
+    bool live[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int i = q0 + 4 * lg + r;
+        lrow[r] = i < S ? lse[(int64_t)bh * S + i] : 0.f;
+        live[r] = i < S && lrow[r] > -INFINITY;                // a fully masked row (lse = -inf) is all zeros
+    }
+    const float inv_keep = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
+    float* obase = out + (int64_t)bh * S * S;
+    for (int kb = 0; kb < nrb; ++kb) {
+        const int j = kb * 16 + lr;
+        f32x4 sacc = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (kb <= rb) {                                         // causal: key blocks 0..rb (wave-uniform)
+#pragma unroll
+            for (int ks = 0; ks < D / 32; ++ks) {
+                uint4 u = make_uint4(0, 0, 0, 0);
+                if (j < S) u = *reinterpret_cast<const uint4*>(kbase + (int64_t)j * rs3 + 32 * ks + 8 * lg);
+                sacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf[ks], *reinterpret_cast<bf16x8*>(&u), sacc, 0, 0, 0);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int i = q0 + 4 * lg + r;
+            float pd = 0.f;
+            if (kb <= rb && live[r] && attn_allowed(i, j, S, L, Kimg)) {
+                const float p = __expf(sacc[r] * scale - lrow[r]);
+                float keep = 1.f;
+                if (drop_p > 0.f)
+                    keep = hash_uniform(seed, (uint32_t)bh, (uint32_t)i, (uint32_t)j) < drop_p ? 0.f : inv_keep;
+                pd = p * keep;
+            }
+            if (i < S && j < S) obase[(int64_t)i * S + j] = pd;
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" {
+
+int rt1_attn_probs(const bf16_t* qkv, const float* lse, float* out, int B, int S, int H, int L, int Kimg, float scale,
+                   float drop_p, uint32_t seed, const uint32_t* seed_dev, hipStream_t st) {
+    if (S > 256 || S < 1 || L < 1 || B < 1 || H < 1) return (int)hipErrorInvalidValue;
+    const int nrb = (S + 15) / 16;
+    hipLaunchKernelGGL(rt1_attn_probs_kernel, dim3(B * H, (nrb + 3) / 4), dim3(256), 0, st, qkv, lse, out, S, H, L,
+                       Kimg, scale, drop_p, seed, seed_dev);
+    return (int)hipGetLastError();
+}
 
 int rt1_attn_keepmask(uint8_t* keep, int BH, int S, float drop_p, uint32_t seed, const uint32_t* seed_dev,
                       hipStream_t st) {

@@ -176,6 +176,9 @@ int rt1_attn_bwd(const rt1_bf16* qkv, const rt1_bf16* out, const rt1_bf16* dout,
 int rt1_attn_bwd_long(const rt1_bf16* qkv, const rt1_bf16* out, const rt1_bf16* dout, const float* lse,
                       rt1_bf16* dqkv, int B, int S, int H, int L, int Kimg, float scale, float drop_p, uint32_t seed,
                       const uint32_t* seed_dev, hipStream_t st);
+// the forward's dropped probabilities, fp32 [B, H, S, S], from qkv and its stored lse (S <= 256; every element written)
+int rt1_attn_probs(const rt1_bf16* qkv, const float* lse, float* out, int B, int S, int H, int L, int Kimg, float scale,
+                   float drop_p, uint32_t seed, const uint32_t* seed_dev, hipStream_t st);
 
 // head.hip (fused action head: gather + logits GEMM + CE + argmax)
 int rt1_action_tokenize(const void* const* comps, const int* kind, const int* dim, int n, const float* low,

@@ -32,6 +32,24 @@ from ..config import RT1Config
 from ..parallel.flat import FlatParameters
 
 
+def saliency(attn: torch.Tensor, maps: torch.Tensor, rows: torch.Tensor, K: int, L: int) -> torch.Tensor:
+    """Which feature positions the predicting rows of the current step read, per frame of the window.
+
+    attn [b, H, S, S] (one layer's probabilities, S = T*L), maps [b, T, K, P] (the TokenLearner's softmax over the P
+    positions of each frame), rows [A] (the rows whose logits predict the current action tokens) -> [b, T, P]:
+
+        w[b, t, k]   = mean over heads and rows of attn[b, h, row, t*L + k],   k < K  (the image tokens of step t)
+        sal[b, t, :] = sum_k w[b, t, k] maps[b, t, k, :]
+
+    Every map sums to 1 over P, so sal[b].sum() is the attention mass that the rows put on image tokens.  Device ops
+    only (rows may be a device tensor): usable inside a captured step."""
+    b, H, S, _ = attn.shape
+    T = maps.shape[1]
+    w = attn.float().index_select(2, rows).mean(dim=(1, 2))                 # [b, S]
+    w = w.reshape(b, T, L)[:, :, :K]                                         # [b, T, K]
+    return torch.einsum("btk,btkp->btp", w, maps.float())
+
+
 class InferenceEngine:
     def __init__(self, model: torch.nn.Module, cfg: Optional[RT1Config] = None, device=None, batch_size: int = 1,
                  graph: Optional[bool] = None, backend: str = "auto"):
@@ -75,6 +93,22 @@ class InferenceEngine:
         self._g = None
         self._out = None
         self.last_logits = None
+        # a model built with return_attention_scores: a rolling window of the TokenLearner maps next to state_img, every
+        # layer's probabilities and the saliency of the last step, all static tensors that a graph replay rewrites
+        self.explain = bool(getattr(m, "_return_attention_scores", False))
+        self.state_maps = self.last_attention = self.last_saliency = None
+        if self.explain:
+            if not m._use_token_learner:
+                raise ValueError("saliency (return_attention_scores in the inference engine) needs use_token_learner="
+                                 "True: without TokenLearner there are no spatial maps to project the attention on")
+            from ..models.efficientnet import feature_map_size
+            self.fmap = feature_map_size(H, W, m._image_tokenizer._tokenizer.net.specs)
+            P, S = self.fmap[0] * self.fmap[1], self.T * self.L
+            heads = [ly.attn.h for ly in m._transformer._layers]
+            self.state_maps = torch.zeros(self.b, self.T, self.K, P, device=dev)
+            self.last_attention = [torch.zeros(self.b, h, S, S, device=dev) for h in heads]
+            self.last_saliency = torch.zeros(self.b, self.T, *self.fmap, device=dev)
+        self.saliency_layer = -1
 
     # ---------------------------------------------------------------- the step (device ops only)
     def _body(self):
@@ -92,6 +126,14 @@ class InferenceEngine:
         logits = m.action_logits(hidden, pos)                                          # (b, A, V)
         tokens = logits.argmax(dim=-1)
         sact.index_copy_(1, ts, tokens.view(self.b, 1, A))
+        if self.explain:
+            smaps = self.state_maps.index_select(1, order)                             # rolled like state_img
+            smaps.index_copy_(1, ts, m.token_maps.to(smaps.dtype))
+            self.state_maps.copy_(smaps)
+            for dst, src in zip(self.last_attention, m.attention_scores):
+                dst.copy_(src)
+            sal = saliency(self.last_attention[self.saliency_layer], self.state_maps, pos, K, L)
+            self.last_saliency.copy_(sal.view(self.last_saliency.shape))
         self.state_img.copy_(simg)
         self.state_act.copy_(sact)
         self.seq_idx.copy_(torch.clamp(self.seq_idx + 1, max=T))
@@ -102,10 +144,13 @@ class InferenceEngine:
         self.state_img.zero_()
         self.state_act.zero_()
         self.seq_idx.zero_()
+        if self.explain:
+            self.state_maps.zero_()
 
     def _capture(self):
         torch.cuda.synchronize(self.device)
         saved = (self.state_img.clone(), self.state_act.clone(), self.seq_idx.clone())
+        saved_maps = self.state_maps.clone() if self.explain else None
         s = torch.cuda.Stream(self.device)
         s.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(s), torch.no_grad():
@@ -118,6 +163,8 @@ class InferenceEngine:
         self.state_img.copy_(saved[0])
         self.state_act.copy_(saved[1])
         self.seq_idx.copy_(saved[2])
+        if self.explain:
+            self.state_maps.copy_(saved_maps)
 
     @torch.no_grad()
     def step(self, image, context) -> Dict[str, torch.Tensor]:

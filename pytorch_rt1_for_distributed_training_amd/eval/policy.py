@@ -59,6 +59,18 @@ class RT1Policy:
     def reset(self):
         self.engine.reset()
 
+    def last_saliency(self, newest: bool = False):
+        """The saliency of the last ``action`` call (``engine.infer.saliency`` on the last layer): a device tensor
+        [b, T, h', w'] over the frames of the window, or, ``newest``, the [h', w'] numpy map of the frame that call was
+        given.  The model must have been built with ``return_attention_scores`` (and TokenLearner)."""
+        e = self.engine
+        if not e.explain:
+            raise ValueError("last_saliency needs a model built with RT1Config(return_attention_scores=True)")
+        if not newest:
+            return e.last_saliency
+        slot = max(min(int(e.seq_idx), e.T) - 1, 0)           # seq_idx was advanced by the step: the slot it wrote
+        return e.last_saliency[0, slot].float().cpu().numpy()
+
     @torch.no_grad()
     def action(self, rgb, instruction_embedding) -> np.ndarray:
         """rgb: (H, W, 3) uint8 frame or (T, H, W, 3) history (last frame used);

@@ -49,7 +49,8 @@ def build_rt1(cfg: RT1Config, pretrained: str = None) -> TransformerNetwork:
         vocab_size=cfg.vocab_size, token_embedding_size=cfg.token_embedding_size, num_layers=cfg.num_layers,
         layer_size=cfg.layer_size, num_heads=cfg.num_heads, feed_forward_size=cfg.feed_forward_size,
         dropout_rate=cfg.dropout_rate, time_sequence_length=cfg.seq_len, crop_size=236,
-        use_token_learner=cfg.use_token_learner, width_coefficient=cfg.width_coefficient,
+        use_token_learner=cfg.use_token_learner, return_attention_scores=cfg.return_attention_scores,
+        width_coefficient=cfg.width_coefficient,
         depth_coefficient=cfg.depth_coefficient, drop_connect_rate=cfg.drop_connect_rate,
         crop_ratio=cfg.crop_ratio)
     path = pretrained or getattr(cfg, "pretrained", None)

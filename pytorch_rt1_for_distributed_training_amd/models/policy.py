@@ -102,6 +102,9 @@ class TransformerNetwork(nn.Module):
         self._loss = None
         self._attention_scores: List[torch.Tensor] = []
         self._use_token_learner = use_token_learner
+        self._return_attention_scores = return_attention_scores
+        # with return_attention_scores: the TokenLearner's softmax maps of the last tokenize_images call, [b, t, K, P] fp32
+        self.token_maps: Optional[torch.Tensor] = None
         _, height, width = input_tensor_space["image"].shape
 
         # registration order == checkpoint key order
@@ -183,7 +186,14 @@ class TransformerNetwork(nn.Module):
         b, t = images.shape[:2]
         frames = images.reshape(b * t, *images.shape[2:])
         frames = preprocess.convert_dtype_and_crop_images(frames, self._crop_ratio, shift)
-        return self._image_tokenizer(frames.reshape(b, t, *frames.shape[1:]), context)
+        keep = self._return_attention_scores and self._use_token_learner
+        if keep:
+            self._image_tokenizer._token_learner.keep_maps = True
+        tokens = self._image_tokenizer(frames.reshape(b, t, *frames.shape[1:]), context)
+        if keep:
+            maps = self._image_tokenizer._token_learner.last_maps                # [b*t, K, P]
+            self.token_maps = maps.reshape(b, t, *maps.shape[1:])
+        return tokens
 
     def assemble_tokens(self, image_tokens: torch.Tensor) -> torch.Tensor:
         """[image tokens, zeroed action tokens] per step -> (b, T*L, E) (``:378-390``)."""

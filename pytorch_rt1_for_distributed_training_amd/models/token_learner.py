@@ -23,6 +23,9 @@ class TokenLearnerModule(nn.Module):
         self.conv2 = nn.Conv2d(bottleneck_dim, num_tokens, 1)
         self.dropout_rate = dropout_rate
         self.num_tokens = num_tokens
+        # keep_maps: each forward leaves its softmax over positions, [N, K, P] fp32 (detached), in last_maps
+        self.keep_maps = False
+        self.last_maps = None
 
     def forward_nhwc(self, feats: torch.Tensor) -> torch.Tensor:
         """feats: (N, P, C) with P = H*W positions -> (N, K, C)."""
@@ -34,6 +37,8 @@ class TokenLearnerModule(nn.Module):
         if self.dropout_rate > 0:
             logits = F.dropout(logits, self.dropout_rate, self.training)
         weights = torch.softmax(logits.float(), dim=1).to(feats.dtype)              # softmax over positions
+        if self.keep_maps:
+            self.last_maps = weights.detach().transpose(1, 2).float().contiguous()
         return torch.bmm(weights.transpose(1, 2), feats)                           # (N, K, C)
 
     def forward(self, inputs: torch.Tensor) -> torch.Tensor:

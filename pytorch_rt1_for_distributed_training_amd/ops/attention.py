@@ -34,24 +34,36 @@ def _allowed(S, L, Kimg, device):
     return m
 
 
+def attn_probs(qkv, lse, L, Kimg, scale, drop_p, seed):
+    """The probabilities that the forward applied to V (dropout included), fp32 [B, H, S, S], rebuilt from its qkv and
+    stored lse by the ``attn_probs`` kernel: what the eager ``masked_attention(..., return_scores=True)`` returns."""
+    return load().attn_probs(qkv, lse, L, Kimg, scale, drop_p, seed, _ctr(qkv))
+
+
 class RT1AttentionFn(torch.autograd.Function):
+    """``want_scores``: -> (out, probabilities [B, H, S, S] fp32), the second non-differentiable."""
+
     @staticmethod
-    def forward(ctx, qkv, L: int, Kimg: int, drop_p: float, seed: int):
+    def forward(ctx, qkv, L: int, Kimg: int, drop_p: float, seed: int, want_scores: bool = False):
         qkv = qkv.contiguous()
         D = qkv.shape[-1]
         scale = 1.0 / math.sqrt(D)
         out, lse = load().attn_fwd(qkv, L, Kimg, scale, drop_p, seed, _ctr(qkv))
         ctx.save_for_backward(qkv, out, lse)
         ctx.args = (L, Kimg, drop_p, seed, scale)
+        if want_scores:
+            probs = attn_probs(qkv, lse, L, Kimg, scale, drop_p, seed)
+            ctx.mark_non_differentiable(probs)
+            return out, probs
         return out
 
     @staticmethod
-    def backward(ctx, dout):
+    def backward(ctx, dout, *_):
         qkv, out, lse = ctx.saved_tensors
         L, Kimg, drop_p, seed, scale = ctx.args
         B, S, _, H, D = qkv.shape
         return attn_backward(qkv, out, dout.to(qkv.dtype).contiguous(), lse, L, Kimg, scale, drop_p, seed), \
-            None, None, None, None
+            None, None, None, None, None
 
     @staticmethod
     def _backward_torch(qkv, out, lse, dout, L, Kimg, drop_p, seed, scale):
@@ -209,12 +221,13 @@ class RT1LayerFn(torch.autograd.Function):
     ``next_ln`` = the next layer's (gamma, beta, eps), returned as three non-differentiable extra outputs (their
     gradient is the next layer's LayerNorm backward, which it runs itself from x3 and the saved statistics).  The LN2
     backward also emits the out-projection's bf16 gradient operand and its bias gradient.  The backward recomputes
-    nothing but P inside the attention kernel."""
+    nothing but P inside the attention kernel.  With ``want_scores`` (the last entry of ``meta``) a fourth
+    non-differentiable output holds the layer's attention probabilities (``attn_probs``, one more launch)."""
 
     @staticmethod
     def forward(ctx, x, g1, b1, wq, bq, wk, bk, wv, bv, wo, bo, g2, b2, wf, bff, aux_xn, aux_mu, aux_rs, meta):
         ext = load()
-        L, Kimg, H, D, p_attn, p_ff, eps1, eps2, next_ln = meta
+        L, Kimg, H, D, p_attn, p_ff, eps1, eps2, next_ln, want_scores = meta
         B, S, E = x.shape
         T = B * S
         x2d = x.reshape(T, E).float().contiguous()
@@ -254,8 +267,13 @@ class RT1LayerFn(torch.autograd.Function):
                 nxt = ext.tf_ln_fwd(x3, gn.float(), bn.float(), epsn)
         ctx.save_for_backward(x2d, xn1, mu1, rs1, qkv, o, lse, x2, xn2, mu2, rs2, Wqkv, wo_b, wf_b, g1, g2)
         ctx.meta = (L, Kimg, H, D, p_attn, p_ff, seed_a, seed_f, scale, B, S, E)
-        ctx.mark_non_differentiable(*nxt)
         ctx.set_materialize_grads(False)        # no zero-filled gradients for the three LN outputs
+        if want_scores:
+            # one extra launch, reading what this forward already holds; nothing above depends on it
+            probs = attn_probs(qkv, lse, L, Kimg, scale, p_attn, seed_a)
+            ctx.mark_non_differentiable(*nxt, probs)
+            return (x3.view(B, S, E), *nxt, probs)
+        ctx.mark_non_differentiable(*nxt)
         return (x3.view(B, S, E), *nxt)
 
     @staticmethod
@@ -291,21 +309,25 @@ class RT1LayerFn(torch.autograd.Function):
                 dWqkv[2 * n:], dbqkv[2 * n:], dwo, dbo, dg2, db2, dwf, dbff, None, None, None, None)
 
 
-def fused_layer(layer, x: torch.Tensor, L: int, Kimg: int, training: bool, aux=None, next_norm=None):
+def fused_layer(layer, x: torch.Tensor, L: int, Kimg: int, training: bool, aux=None, next_norm=None, scores=None):
     """One fused layer: returns (x3, aux for the next layer or None).  ``aux`` = (LN1(x), mean, rstd) from the previous
-    layer's epilogue; ``next_norm`` = the next layer's norm_1 (its LayerNorm is formed in this layer's epilogue)."""
+    layer's epilogue; ``next_norm`` = the next layer's norm_1 (its LayerNorm is formed in this layer's epilogue).
+    ``scores``: a list; a layer built with ``return_attention_scores`` appends its [B, H, S, S] fp32 probabilities."""
     att = layer.attn
     p_attn = att.dropout.p if training else 0.0
     p_ff = layer.dropout_1.p if training else 0.0
     nl = (next_norm.weight, next_norm.bias, next_norm.eps) if next_norm is not None else None
-    meta = (L, Kimg, att.h, att.key_dim, p_attn, p_ff, layer.norm_1.eps, layer.norm_2.eps, nl)
+    want = scores is not None and layer._return_attention_scores
+    meta = (L, Kimg, att.h, att.key_dim, p_attn, p_ff, layer.norm_1.eps, layer.norm_2.eps, nl, want)
     e = _empty(x.device)
     ax = aux if aux is not None else (e, e, e)
     out = RT1LayerFn.apply(x, layer.norm_1.weight, layer.norm_1.bias, att.q_linear.weight, att.q_linear.bias,
                            att.k_linear.weight, att.k_linear.bias, att.v_linear.weight, att.v_linear.bias,
                            att.out.weight, att.out.bias, layer.norm_2.weight, layer.norm_2.bias, layer.ff.weight,
                            layer.ff.bias, ax[0], ax[1], ax[2], meta)
-    return out[0], (tuple(out[1:]) if nl is not None else None)
+    if want:
+        scores.append(out[4].detach())
+    return out[0], (tuple(out[1:4]) if nl is not None else None)
 
 
 def fused_layer_supported(layer) -> bool:
@@ -320,14 +342,19 @@ def fused_qkv_weights(attn):
     return w, b
 
 
-def transformer_layer(layer, x: torch.Tensor, L: int, Kimg: int, training: bool) -> torch.Tensor:
-    """One RT-1 layer (``_TransformerLayer``) with the fused QKV GEMM and the HIP attention."""
+def transformer_layer(layer, x: torch.Tensor, L: int, Kimg: int, training: bool, scores=None) -> torch.Tensor:
+    """One RT-1 layer (``_TransformerLayer``) with the fused QKV GEMM and the HIP attention; ``scores`` as in
+    ``fused_layer``."""
     B, S, E = x.shape
     att = layer.attn
     x1 = layer.norm_1(x)
     w, b = fused_qkv_weights(att)
     qkv = F.linear(x1, w, b).view(B, S, 3, att.h, att.key_dim)
     p = att.dropout.p if training else 0.0
-    o = RT1AttentionFn.apply(qkv, L, Kimg, p, _seed(p))
+    if scores is not None and layer._return_attention_scores:
+        o, probs = RT1AttentionFn.apply(qkv, L, Kimg, p, _seed(p), True)
+        scores.append(probs.detach())
+    else:
+        o = RT1AttentionFn.apply(qkv, L, Kimg, p, _seed(p))
     x = x + att.out(o.reshape(B, S, att.h * att.value_dim))
     return x + layer.dropout_1(layer.ff(layer.norm_2(x)))

@@ -139,11 +139,20 @@ class FusedRT1:
         if not tok._use_token_learner:
             return feats.reshape(b, t, feats.shape[1], -1)
         from .token_learner import supported, token_learner
-        if self.dtype == torch.bfloat16 and supported(tok._token_learner, feats.shape[1]):
-            tokens = token_learner(tok._token_learner, feats)             # csrc/kernels/tokenlearner.hip
+        keep = getattr(model, "_return_attention_scores", False)          # then model.token_maps = [b, t, 8, P] fp32
+        tl = tok._token_learner
+        if self.dtype == torch.bfloat16 and supported(tl, feats.shape[1]):
+            if keep:
+                tokens, maps = token_learner(tl, feats, True)             # the forward kernel's own softmax
+            else:
+                tokens = token_learner(tl, feats)                         # csrc/kernels/tokenlearner.hip
         else:
+            tl.keep_maps = keep
             with self._autocast():
-                tokens = tok._token_learner.forward_nhwc(feats)
+                tokens = tl.forward_nhwc(feats)
+            maps = tl.last_maps
+        if keep:
+            model.token_maps = maps.reshape(b, t, *maps.shape[1:])
         return tokens.reshape(b, t, tokens.shape[1], -1)
 
     def transformer_hidden(self, model, tokens):
@@ -157,6 +166,9 @@ class FusedRT1:
         else:
             with self._autocast():
                 x = tf.embed(tokens)
+        # layers built with return_attention_scores append their [B, H, S, S] fp32 probabilities (the attn_probs kernel on
+        # the qkv / lse of this very forward); the others add no launch and the list stays empty
+        scores = []
         if fused:
             # fp32 residual stream through the fused HIP layers (LN / residual / dropout / attention kernels)
             x = x.float()
@@ -164,12 +176,12 @@ class FusedRT1:
             aux = None
             for i, layer in enumerate(layers):
                 nxt = layers[i + 1].norm_1 if i + 1 < len(layers) else None
-                x, aux = fused_layer(layer, x, L, Kimg, tf.training, aux, nxt)
+                x, aux = fused_layer(layer, x, L, Kimg, tf.training, aux, nxt, scores)
         else:
             with self._autocast():
                 for layer in tf._layers:
-                    x = transformer_layer(layer, x, L, Kimg, tf.training)
-        model._attention_scores = []
+                    x = transformer_layer(layer, x, L, Kimg, tf.training, scores)
+        model._attention_scores = scores
         return x
 
     def action_loss(self, model, logits, targets, b, t):

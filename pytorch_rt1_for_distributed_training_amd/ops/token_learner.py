@@ -17,7 +17,7 @@ BF = torch.bfloat16
 
 class TokenLearnerFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, feats, ln_w, ln_b, w1, b1, w2, b2, eps: float):
+    def forward(ctx, feats, ln_w, ln_b, w1, b1, w2, b2, eps: float, want_maps: bool = False):
         from .backbone import _bf
         ext = load()
         x = feats.to(BF).contiguous()
@@ -27,10 +27,14 @@ class TokenLearnerFn(torch.autograd.Function):
                                         b1.float().contiguous(), W2, b2.float().contiguous())
         ctx.save_for_backward(x, mu, rs, z1, s, ln_w, ln_b, W1, W2)
         ctx.shapes = (w1.shape, w2.shape)
+        if want_maps:
+            maps = s.detach().clone()             # the softmax over positions [N, 8, P] fp32 (s itself stays saved)
+            ctx.mark_non_differentiable(maps)
+            return out, maps
         return out
 
     @staticmethod
-    def backward(ctx, dout):
+    def backward(ctx, dout, *_):
         from .backbone import wgrad
         x, mu, rs, z1, s, ln_w, ln_b, W1, W2 = ctx.saved_tensors
         w1_shape, w2_shape = ctx.shapes
@@ -42,7 +46,7 @@ class TokenLearnerFn(torch.autograd.Function):
         dW2 = w2p[:, :64].contiguous().view(w2_shape)
         db2 = w2p[:, 64].contiguous()
         g = load().colsum(pg)                                                      # [2, 512]
-        return dx, g[0], g[1], dW1, db1, dW2, db2, None
+        return dx, g[0], g[1], dW1, db1, dW2, db2, None, None
 
 
 def supported(tl, positions: int) -> bool:
@@ -50,7 +54,11 @@ def supported(tl, positions: int) -> bool:
             and tl.conv1.in_channels == 512 and load().tl_supported(positions, 512, 64, 8))
 
 
-def token_learner(tl, feats: torch.Tensor) -> torch.Tensor:
-    """feats [N, P, 512] (bf16) -> tokens [N, 8, 512] bf16."""
+def token_learner(tl, feats: torch.Tensor, want_maps: bool = False):
+    """feats [N, P, 512] (bf16) -> tokens [N, 8, 512] bf16; ``want_maps``: -> (tokens, softmax maps [N, 8, P] fp32, the
+    forward kernel's own ``s``, non-differentiable)."""
+    if want_maps:
+        return TokenLearnerFn.apply(feats, tl.layerNorm.weight, tl.layerNorm.bias, tl.conv1.weight, tl.conv1.bias,
+                                    tl.conv2.weight, tl.conv2.bias, tl.layerNorm.eps, True)
     return TokenLearnerFn.apply(feats, tl.layerNorm.weight, tl.layerNorm.bias, tl.conv1.weight, tl.conv1.bias,
                                 tl.conv2.weight, tl.conv2.bias, tl.layerNorm.eps)
