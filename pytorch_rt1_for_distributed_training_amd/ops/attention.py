@@ -16,8 +16,8 @@ import torch.nn.functional as F
 
 from . import rng, switches
 from ._ext import load
+from .linear import _bf, proj, token_wgrad
 from ..models.transformer import rt1_attention_mask
-from ..parallel.flat import defer_partials
 
 BF = torch.bfloat16
 BWD_MAX_S = 96     # single-kernel attn_bwd covers S <= 96 (T <= 8); longer histories (<= 256) use attn_bwd_long
@@ -101,87 +101,12 @@ def attn_backward(qkv, out, dout, lse, L, Kimg, scale, drop_p, seed):
     return ext.attn_bwd_long(qkv, out, dout, lse, L, Kimg, scale, drop_p, seed, _ctr(qkv))
 
 
-# The projections stay on the recorded hipBLASLt solutions (tuning/): gemm.hip beat UNtuned hipBLASLt on the fused
-# Q/K/V forward, the FF forward and the out / FF data gradients in isolation (profiles/r4_gemm_bench_lds_store.log) but
-# not the tuned library in the step (-0.3 %, profiles/r4_tf_gemm_lds_ab.log), and the full-row gemm path with the
-# LayerNorm in the epilogue (tfrow.hip) was 2 ms/step slower (profiles/r5_tfrow_ab.log); both were removed.
-
-
-# (N, K, nn) -> gemm.hip tile config for the projections where its small tiles beat the tuned library in the step
-# (tools/bench_tf_gemms.py); the rest stay on hipBLASLt
-# (in the step: FF / out data gradients 14.2 / 20.6 us vs the library's 16.2 / 21.2; the forward products stayed on the
-# library, 19 vs 17 us on 64 x 64 tiles -- gpurun_out/trN vs trN_film kernel traces)
-_TF_GEMM_CFG = {(512, 512, True): 3, (1024, 512, True): 4}
-TF_GEMM = _TF_GEMM_CFG if switches.on("tf_gemm") else {}
-
-
-def _proj(a, w, nn: bool = False):
-    """a @ w^T (w [N, K], a Linear weight) or, nn, a @ w (w [K, N]: the data gradient through that weight)."""
-    cfg = TF_GEMM.get((w.shape[1], w.shape[0], True) if nn else (w.shape[0], w.shape[1], False))
-    if cfg is not None and a.shape[0] >= 1024:
-        return load().gemm(a, w, nn, cfg=cfg)[0]
-    return torch.mm(a, w) if nn else torch.mm(a, w.t())
-
-
 _QKV = {}     # data_ptr(q weight) -> (Wqkv [3HD, E], bqkv [3HD]) bf16, packed per step by FusedRT1._refresh_shadow
 
 
 def set_qkv_packs(packs):
     global _QKV
     _QKV = packs
-
-
-def _bfw(w):
-    from .backbone import _bf
-    return _bf(w)
-
-
-def _mm32(a, b):
-    try:
-        return torch.mm(a, b, out_dtype=torch.float32)
-    except (TypeError, RuntimeError):
-        return torch.mm(a, b).float()
-
-
-# projection weight gradients on the streaming MFMA kernel (csrc/kernels/wgrad.hip, split over the T = B*S token rows,
-# fixed-order reduce): hipBLASLt runs dW = dY^T X with K = 8448 and a 512x512 output on 16 macro tiles, ~5 % of its
-# roofline (tools/gemm_census.py)
-TF_WGRAD = switches.on("tf_wgrad")
-
-
-def _tf_wgrad_cfg(M: int, Co: int):
-    """(tile variant, row splits) of wgrad.hip for the transformer's short reductions (T = B x S tokens, 8448 at
-    b128): the automatic choice aims at ~512 workgroups of the widest tile, right for the encoder's millions of rows
-    but here every split writes a whole fp32 [Co, Ci] partial.  Swept per shape (tools/bench_wgrad_short.py,
-    profiles/r5_wgrad_short.log): 128 x 128 tiles with ~1056-row splits for the 3072-wide QKV gradient (105.6 -> 56.2
-    us), 64 x 128 tiles with ~704-row splits for the 512-wide ones (58.4 -> 31.2, 44.0 -> 23.8 us)."""
-    if M > 65536:
-        return -1, -1
-    if Co >= 2048:
-        return 2, max(1, min(16, M // 1056))
-    return 1, max(1, min(16, M // 704))
-
-
-def _wgrad_bias(dy, x, ok: bool = True):
-    """(dW = dy^T x, db = sum_rows dy) of a parameter pair: the column sums of dy come from the wgrad kernel's staged
-    rows and share its split partials' fixed-order sum (one launch instead of a colsum re-reading dy)."""
-    Co, Ci = dy.shape[1], x.shape[1]
-    if TF_WGRAD and dy.dtype == BF and x.dtype == BF and Co % 8 == 0 and Ci % 8 == 0:
-        v, s = _tf_wgrad_cfg(dy.shape[0], Co)
-        flat = defer_partials(load().wgrad(dy.contiguous(), x.contiguous(), variant=v, splits=s, partials=True,
-                                           sums=True), ok)
-        return flat[:Co * Ci].view(Co, Ci), flat[Co * Ci:]
-    return _wgrad(dy, x, True, ok), load().colsum(dy)
-
-
-def _wgrad(dy, x, final: bool = False, ok: bool = True):
-    """dW = dy^T x: dy [T, Co], x [T, Ci] bf16 -> fp32 [Co, Ci].  ``final``: a parameter gradient as is (``ok``: every
-    row slice of it reaches a parameter that requires one), its split-K sum left to the flat gather."""
-    if TF_WGRAD and dy.dtype == BF and x.dtype == BF and dy.shape[1] % 8 == 0 and x.shape[1] % 8 == 0:
-        v, s = _tf_wgrad_cfg(dy.shape[0], dy.shape[1])
-        out = load().wgrad(dy.contiguous(), x.contiguous(), variant=v, splits=s, partials=final)
-        return defer_partials(out, ok) if final else out
-    return _mm32(dy.t(), x)
 
 
 def _seed(p: float) -> int:
@@ -239,7 +164,7 @@ class RT1LayerFn(torch.autograd.Function):
         if pk is not None:
             Wqkv, bqkv = pk                                                     # packed with the weight shadow
         else:
-            Wqkv = torch.cat([_bfw(wq), _bfw(wk), _bfw(wv)], 0)                # [3*H*D, E]
+            Wqkv = torch.cat([_bf(wq), _bf(wk), _bf(wv)], 0)                   # [3*H*D, E]
             bqkv = torch.cat([bq, bk, bv]).to(BF)
         qkv = torch.addmm(bqkv, xn1, Wqkv.t()).view(B, S, 3, H, D)
         scale = 1.0 / math.sqrt(D)
@@ -247,16 +172,16 @@ class RT1LayerFn(torch.autograd.Function):
         ctr = _ctr(x)
         o, lse = ext.attn_fwd(qkv, L, Kimg, scale, p_attn, seed_a, ctr)
         o2d = o.view(T, H * D)
-        wo_b, wf_b = _bfw(wo), _bfw(wf)
+        wo_b, wf_b = _bf(wo), _bf(wf)
         empty = _empty(x.device)
         nxt = (empty, empty, empty)
         if TF_FUSE_LN:
-            x2, xn2, mu2, rs2 = ext.tf_resid(x2d, _proj(o2d, wo_b), bo.float().contiguous(), 0.0, 0, None,
+            x2, xn2, mu2, rs2 = ext.tf_resid(x2d, proj(o2d, wo_b), bo.float().contiguous(), 0.0, 0, None,
                                              g2.float(), b2.float(), eps2)
         else:
-            (x2,) = ext.tf_resid(x2d, _proj(o2d, wo_b), bo.float().contiguous(), 0.0, 0)
+            (x2,) = ext.tf_resid(x2d, proj(o2d, wo_b), bo.float().contiguous(), 0.0, 0)
             xn2, mu2, rs2 = ext.tf_ln_fwd(x2, g2.float(), b2.float(), eps2)
-        ff = _proj(xn2, wf_b)
+        ff = proj(xn2, wf_b)
         if next_ln is not None and TF_FUSE_LN:
             gn, bn, epsn = next_ln
             x3, *nxt = ext.tf_resid(x2, ff, bff.float().contiguous(), p_ff, seed_f, ctr, gn.float(), bn.float(), epsn)
@@ -289,21 +214,21 @@ class RT1LayerFn(torch.autograd.Function):
         ctr = _ctr(dx3)
         dh, dbff = ext.tf_drop_bwd(dx3, p_ff, seed_f, ctr)
         nig = ctx.needs_input_grad
-        dwf = _wgrad(dh, xn2, True, nig[13])
+        dwf = token_wgrad(dh, xn2, True, nig[13])
         o2d = o.view(T, H * D)
         # LN2 backward (+ the residual grad dx3); its bf16 copy of dx2 is the out-projection's gradient operand
         if TF_FUSE_LN:
-            dx2, dg2, db2, da, dbo = ext.tf_ln_bwd(_proj(dh, wf_b, True), x2, mu2, rs2, g2.float(), dx3, True)
+            dx2, dg2, db2, da, dbo = ext.tf_ln_bwd(proj(dh, wf_b, True), x2, mu2, rs2, g2.float(), dx3, True)
         else:
-            dx2, dg2, db2 = ext.tf_ln_bwd(_proj(dh, wf_b, True), x2, mu2, rs2, g2.float(), dx3)
+            dx2, dg2, db2 = ext.tf_ln_bwd(proj(dh, wf_b, True), x2, mu2, rs2, g2.float(), dx3)
             da, dbo = ext.tf_drop_bwd(dx2, 0.0, 0)
         # attention branch: out-projection, attention, QKV projection, LN1 (+ residual)
-        dwo = _wgrad(da, o2d, True, nig[9])
-        do = _proj(da, wo_b, True).view(B, S, H, D)
+        dwo = token_wgrad(da, o2d, True, nig[9])
+        do = proj(da, wo_b, True).view(B, S, H, D)
         dqkv = attn_backward(qkv, o, do, lse, L, Kimg, scale, p_attn, seed_a)
         dq2d = dqkv.view(T, 3 * H * D)
-        dWqkv, dbqkv = _wgrad_bias(dq2d, xn1, all(nig[3:9]))
-        dx, dg1, db1 = ext.tf_ln_bwd(_proj(dq2d, Wqkv, True), x2d, mu1, rs1, g1.float(), dx2)
+        dWqkv, dbqkv = token_wgrad(dq2d, xn1, ok=all(nig[3:9]), bias=True)
+        dx, dg1, db1 = ext.tf_ln_bwd(proj(dq2d, Wqkv, True), x2d, mu1, rs1, g1.float(), dx2)
         n = H * D
         return (dx.view(B, S, E), dg1, db1, dWqkv[:n], dbqkv[:n], dWqkv[n:2 * n], dbqkv[n:2 * n],
                 dWqkv[2 * n:], dbqkv[2 * n:], dwo, dbo, dg2, db2, dwf, dbff, None, None, None, None)

@@ -16,7 +16,8 @@ backward  tail_bwd_reduce (FiLM grads + BN3 partials) -> BN3 backward-apply -> d
 
 Which kernels run each stage of a block is decided once, by ``plan_block`` (a ``BlockRoute``: one short string per
 stage), from the block's shape and the ``RouteFlags`` read from ops/switches.py; the forward plans, the backward reads
-the plan.  The comments on ``RouteFlags`` say what each path is and which log decided its default.
+the plan.  The comments on ``RouteFlags`` (ops/linear.py, with the planners and executors of every 1x1-conv product and
+weight gradient) say what each path is and which log decided its default.
 
 Saved per block: x, y2, y3 (bf16), y1 only outside x-mode, A only when the project backward needs it, the SE vectors
 (pool, h, gate) and per-channel constants.
@@ -25,15 +26,15 @@ from __future__ import annotations
 
 import functools
 import os
-from dataclasses import dataclass, fields
+from dataclasses import dataclass
 from typing import List, Optional
 
 import torch
 import torch.nn.functional as F
 
-from . import switches
 from ._ext import load
-from ..parallel.flat import defer_partials
+from .linear import (FLAGS, Product, RouteFlags, _GEMM_PROJ_DGRAD_TILE, _GEMM_PROJ_TILE, _Z_GEMM_TILE, _bf, _partials,
+                     _pw_blocks, gram_moments, lin, lin_bn, wgrad, wgrad_mfma_preferred)
 
 ACT_NONE, ACT_SILU = 0, 1
 MAX_BLOCKS = 2048   # ~8 workgroups per CU on 256 CUs: upper bound for persistent tile loops / partial rows
@@ -42,21 +43,6 @@ BF = torch.bfloat16
 
 def _ext():
     return load()
-
-
-def _mm(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
-    """bf16 x bf16 -> bf16 GEMM on hipBLASLt (fp32 accumulate)."""
-    return torch.mm(a, b)
-
-
-PW_BLOCKS = 2048
-
-
-def _pw_blocks(M: int) -> int:
-    """Grid cap of the skinny pointwise GEMM (pwgemm.hip): 512 on the 38x38 maps (M ~ 1.1 M rows: 135-143 vs 145-157
-    us for the expand / project convs, 270 vs 286 us for the BN3-backward dgrad, per-site sweep
-    tools/bench_grid_sites.py, profiles/r5_grid_sites.log), PW_BLOCKS elsewhere (flat or worse below 2048)."""
-    return 512 if 500_000 <= M <= 2_000_000 else PW_BLOCKS
 
 
 # per-(map side, channels) grid cap of the fused depthwise backward where the per-site sweep beat MAX_BLOCKS by more
@@ -78,165 +64,6 @@ def _mark(name: str):
         TIMING_EVENTS.append((name, ev))
 
 
-# tile tables behind RouteFlags' gemm_proj / gemm_proj_dgrad / z_gemm: (Ce, Cout) or (Ce, Cin) -> gemm.hip tile config
-_GEMM_PROJ_TILE = {(1392, 232): 1, (816, 232): 1}
-_GEMM_PROJ_DGRAD_TILE = {(1392, 232): 0, (816, 232): 0}
-_Z_GEMM_TILE = {(1392, 232): -1, (2304, 384): -1}
-
-
-@dataclass(frozen=True)
-class RouteFlags:
-    """The ops/switches.py switches that route the backbone, one field per switch of the same name.  ``FLAGS`` is the
-    process's set (``RT1_AB`` applied); ``plan_block`` turns a set and a block's shape into a ``BlockRoute``."""
-    # tall-skinny MFMA kernel for wide-K / narrow-N 1x1 convs (switch pw_tall=0 routes them to hipBLASLt)
-    pw_tall: bool
-    # the wide-N top / block-25 expand 1x1 convs (K = 384 -> N = 1536 / 2304, M = 76,800) on gemm256.hip's 256 x 256
-    # LDS-DMA tiles with the BN-statistics epilogue: 126 / 184 us against 138-164 / 196-249 us for the library,
-    # gemm.hip and pw_wide (tools/bench_gemm256.py, profiles/r5_gemm256_bench.log), and the bn_stats pass over the
-    # 1536 / 2304-wide output (61 / 94 us per step) disappears.  g256=0: the pw_wide + bn_stats path.
-    g256: bool
-    wgrad_mfma: bool
-    gram_sx: bool
-    dw_fused: bool      # fused stride-1 depthwise backward
-    # stride-2 blocks through the unified stride-2 kernel (dw_bwd_uni_s2_kernel) instead of bn_bwd_apply + data + weight
-    dw_s2_fused: bool
-    # dw_bwd_fused kernel variant: 1 = unified single-pass kernel (dw_bwd_uni_kernel), 0 = the two-pass kernel
-    dw_variant: int
-    # ... and, for the non-expand residual block 1, in the unified depthwise backward's store
-    dw_res: bool
-    pw_pro: bool        # project-conv operand prologue
-    # (not in the tall-skinny kernel of blocks 8-17: the 2 transcendentals per element make that HBM-bound GEMM
-    # VALU-bound, 0.1-0.4 ms/step slower than bn_apply + the plain kernel -- profiles/r2_pw_tall_pro_ab.log,
-    # profiles/r3_pw_tall_pro_ab.log; the kernel keeps the prologue, tests/test_pwgemm_gpu.py)
-    # project-conv backward of the skinny blocks from (dy3, y2) per frame (csrc/kernels/projbwd.hip): the SE / BN2
-    # backward sums and dWp come out of one pass, so the forward no longer stores the operand A and the backward no
-    # longer reads A (dWp) nor dA (se_bn_bwd_reduce)
-    proj_bwd: bool
-    # squeeze-excitation MLP forward / backward as the fused se.hip kernels (se_fwd / se_bwd) instead of hipBLASLt
-    # addmm/mm + elementwise launches.  The round-2 pair was 2.5-5x slower (profiles/r2_se_fused_ab.log: per-frame dot
-    # products as long dependent FMA chains on 96 workgroups); the round-3 kernels (tiled split-K row products, sliced
-    # frame reductions) beat the library path: 1278-1282 -> 1293-1295 samples/s same-box A/B (profiles/r3_se_fused_ab.log).
-    se_fused: bool
-    # Rounds 3-4 ran it on one rank only: the two-rank rehearsal (two processes on one GPU) saw SE fc1 weight gradients
-    # differ run to run.  Root cause (profiles/r4_se_dp_rootcause.md): a v_pk_fma_f32 with a high-element op_sel in
-    # se_wsum_part occasionally lost its low-lane product for 16 lanes -- dw1 came out as the exact sum minus one frame's
-    # term.  The SE kernels are now built without packed fp32 (NO_PACKED_FP32, tests/test_isa_audit.py) and the fused
-    # path is on for any world size.
-    # the stem's BatchNorm + SiLU applied inside block 0 (StemPreFn): no separate activated stem tensor
-    stem_in_block0: bool
-    # ... and the stem BN's backward-apply folded into the stem weight-gradient kernel's staging: block 0
-    # hands the stem the gradient of silu(bn(x)) plus the BN backward constants through a StemLink instead of writing
-    # the [N, 150, 150, 40] dy (one write + one read of 1.4 GB per step at b128)
-    stem_bn_bwd: bool
-    # y-free expand backward (pwbwd.hip pw_bwd_z): the unified depthwise backward stores dz = dA1 * silu'(bn1(y1)) and
-    # the expand dgrad / wgrad are rewritten over the block input x (dy1 = k1*dz + k2*(x @ We^T) + k0), so the Ce-wide
-    # y1 is not read a second time in the backward
-    pw_bwd_z: bool
-    # ... also for the wide expand convs whose dgrad runs on the tall-skinny kernel (blocks 9-17: Cin 96 / 136).  The first
-    # version (library GEMMs for x @ Mk and G, a VALU Mk kernel) measured net slower (profiles/r2_pw_z_wide_ab.log); this
-    # one folds x @ Mk + r0 into the dgrad's K loop (pw_tall_tail) and runs G on the MFMA weight-gradient kernel.
-    pw_z_wide: bool
-    # ... and for the deep blocks 19-24 (expand 232 -> 1392), whose data gradient runs on gemm.hip's two-segment kernel
-    # (gemm_tail: dz . (diag(k1) We) + x . Mk + r0 + dout * fmul in one pass).  Replaces the bn_bwd_apply pass over the
-    # Ce-wide (dA1, y1) -> dy1, the hipBLASLt dgrad of dy1 and the add_scaled_ residual pass.  (Ce, Cin) -> gemm.hip tile
-    # config (-1: automatic).  Blocks 13-18 keep the tall-skinny pw_tall_tail (faster at N = 96 / 136).  Measured
-    # step-neutral (profiles/r3_z_gemm_ab.log: 1297-1301 samples/s either way; the removed passes are paid for by the
-    # slower-than-library gemm.hip tiles at N = 232 / 384), on by default for 12 fewer launches and 7 fewer hipBLASLt
-    # GEMMs per step.  z_gemm=1 (default since the round-5 re-check, profiles/r5_switch_recheck_ab.log: +0.15 %): blocks
-    # 19-24 only; 2: also block 25's 2304 -> 384; 0: the bn_bwd_apply + library path.
-    z_gemm: str
-    # y1-free expand blocks ("x-mode", csrc/kernels/dw/dw_stage.h stage_xmfma + xexpand.hip): the expand output y1 is never
-    # written.  BN1's batch statistics come from the block input's Gram matrix (sum y1 = We sum x, sum y1^2 = w^T G w),
-    # the depthwise forward and its unified backward recompute y1 = x @ We^T per staged tile on MFMA, and the expand
-    # backward is the dz-mode pw_bwd_z (it reads dz and x only).  Removes the expand GEMM's write of y1 and both depthwise
-    # reads of it.  The kernels cover blocks 2-8 (Cin <= 48), but the depthwise backward is VALU-issue bound and holds
-    # its K x K weight-gradient accumulators in registers: recomputing y1 there (MFMA staging, LDS for the centres) made
-    # the backward of blocks 3-8 slower than the y1 bytes it saves, so by default only block 2 (150x150 -> 75x75, 5 GB of
-    # y1 per step) runs y1-free (profiles/r3_xmode_ab.md).  xmode=all: every supported block; 0: none.
-    xmode: str
-    # BN1 of the wide expand convs (blocks 9-25: Cin 96-384 -> Ce 576-2304 on pwgemm.hip's wide kernel, no statistics
-    # epilogue) from G = x^T x and sx = sum x -- the same wgrad(x, x) / colsum(x) the dz-mode expand backward needs, now
-    # computed once in the forward and handed to the backward -- instead of a bn_stats pass over the 6x wider y1
-    # (65-130 us per block: profiles/r4_pmc_bytes.md).  gram_bn=0: the bn_stats pass.
-    gram_bn: bool
-    # Project convs of the deep blocks on the tiled MFMA GEMM (csrc/kernels/gemm.hip) with the operand prologue
-    # A = silu(bn2(y2)) * gate and the BN3-statistics epilogue: replaces bn_apply (read y2, write A) + the hipBLASLt GEMM
-    # (read A) + bn_stats (read y3); A is still stored (by the first N tile) for the weight gradient.  (Ce, Cout) -> tile
-    # config, from tools/bench_gemm_mfma.py (profiles/r3_gemm_bench.log: 1.38-1.42x over the three launches); the
-    # K = 2304 / 1392 -> 384 shapes stay on the library (0.7x).
-    gemm_proj: bool
-    # ... and their data gradients dA = dy3 @ Wp (NN; profiles/r3_gemm_bench.log "proj19 dgrad": 1.32x over hipBLASLt)
-    gemm_proj_dgrad: bool
-    # the residual path's gradient added in the wide dz-mode dgrad's epilogue instead of an add_scaled_ pass
-    tall_res: bool
-
-    @classmethod
-    def from_switches(cls, get=switches.get) -> "RouteFlags":
-        cast = {"bool": lambda v: v != "0", "int": int, "str": str}
-        return cls(**{f.name: cast[f.type](get(f.name)) for f in fields(cls)})
-
-    # the tables the switches stand for
-    g256_stats = property(lambda f: {(384, 1536), (384, 2304)} if f.g256 else set())        # (K, N)
-    gemm_proj_cfg = property(lambda f: _GEMM_PROJ_TILE if f.gemm_proj else {})
-    gemm_proj_dgrad_cfg = property(lambda f: _GEMM_PROJ_DGRAD_TILE if f.gemm_proj_dgrad else {})
-    z_gemm_cfg = property(lambda f: {"0": {}, "2": _Z_GEMM_TILE}.get(f.z_gemm, {(1392, 232): -1}))
-    # (Cin, Ce, k, s) of the y1-free blocks; None: every supported block
-    xmode_shapes = property(lambda f: {"0": set(), "all": None}.get(f.xmode, {(24, 144, 3, 2)}))
-
-
-FLAGS = RouteFlags.from_switches()
-_SHADOW = None  # data_ptr(fp32 master weight) -> bf16 view of the per-step shadow (FusedRT1.attach_flat)
-
-
-def set_weight_shadow(views):
-    global _SHADOW
-    _SHADOW = views
-
-
-def _bf(w: torch.Tensor) -> torch.Tensor:
-    """bf16 copy of a weight: the per-step shadow when one is attached, else a cast."""
-    if _SHADOW is not None:
-        s = _SHADOW.get(w.data_ptr())
-        if s is not None and s.shape == w.shape:
-            return s
-    return w.to(BF)
-
-
-def _lin(a: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
-    """1x1 conv as a @ w^T for a [M, K] bf16, w [N, K] bf16.
-
-    The skinny high-resolution shapes (K, N <= 288; HBM-bound) run on the MFMA streaming kernel of
-    ``csrc/kernels/pwgemm.hip`` (86-100 % of the HBM roofline vs 15-70 % for hipBLASLt's macro tiles), the
-    wide-K narrow-N ones on ``pwtall.hip``; the rest stay on hipBLASLt."""
-    ext = _ext()
-    if ext.pw_gemm_supported(a.shape[1], w.shape[0]):
-        return ext.pw_gemm(a, w.contiguous(), _pw_blocks(a.shape[0]))[0]
-    if FLAGS.pw_tall and a.shape[0] >= 4096 and ext.pw_tall_preferred(a.shape[1], w.shape[0]):
-        # wide reduction, narrow output (project convs, expand data-gradients; N <= 144): csrc/kernels/pwtall.hip
-        return ext.pw_tall(a.contiguous(), w.contiguous())[0]
-    return torch.mm(a, w.t())
-
-
-def _lin_bn(a: torch.Tensor, w: torch.Tensor, bnc: "BNCtx", training: bool, pro=None):
-    """1x1 conv + the consumer BatchNorm's constants; in training the batch statistics come from the
-    GEMM epilogue (one pass over the output) when the MFMA kernel covers the shape.  ``pro = (scale, shift, gate,
-    hw)`` makes the operand silu(a*scale + shift) * gate inside the GEMM (project convs, plan_block's "pw_gemm")."""
-    ext = _ext()
-    if pro is not None:
-        sc, sh, gate, hw, store = pro         # proj_fwd "pw_gemm": pw_gemm-supported shapes only
-        res = ext.pw_gemm(a, w.contiguous(), _pw_blocks(a.shape[0]), training, sc, sh, gate, hw, store)
-        consts = bnc.train_consts(res[1], res[2], a.shape[0]) if training else bnc.eval_consts()
-        return res[0], consts, (res[-1] if store else None)
-    if training and ext.pw_stats_supported(a.shape[1], w.shape[0]):
-        y, ps, pq = ext.pw_gemm(a, w.contiguous(), _pw_blocks(a.shape[0]), True)
-        return y, bnc.train_consts(ps, pq, a.shape[0])
-    if training and (a.shape[1], w.shape[0]) in FLAGS.g256_stats:
-        y, ps, pq = ext.gemm256(a, w.contiguous(), False, stats=True, bn=256)
-        return y, bnc.train_consts(ps, pq, a.shape[0])
-    y = _lin(a, w)
-    return y, _bn_train_or_eval(bnc, training, y)
-
-
 def _pw_bwd_blocks(M: int, z: bool = False) -> int:
     """Grid cap of the fused expand backward (pwbwd.hip), from sweeps at 768 frames
     (tools/scratch/pwbwd_grid_sweep.py, profiles/r2_pwbwd_grid_sweep.log): the 150x150 block wants 4096
@@ -255,33 +82,6 @@ def _dw_wgrad_blocks(C: int) -> int:
     included): the <= 144-channel high-resolution layers keep improving up to 4096 workgroups (-12 % vs 1024),
     the wider ones are flat from 1024 to 2048."""
     return 4096 if C <= 144 else 2048
-
-
-def _mm_f32(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
-    """bf16 x bf16 with fp32 output (weight gradients, reduction over millions of rows)."""
-    try:
-        return torch.mm(a, b, out_dtype=torch.float32)
-    except (TypeError, RuntimeError):
-        return torch.mm(a, b).float()
-
-
-def _wgrad_splits(M: int, out_elems: int) -> int:
-    """Split-K factor of the weight-gradient batched GEMM, fitted to MI355X sweeps of the encoder's shapes
-    (``tools/debug/wgrad_sweep.py``; 1.2-1.8x faster than a rows-per-split rule): the best split keeps
-    ~4-70 k rows per batch entry, enough batch entries to fill the chip, and few fp32 partials to sum."""
-    if M >= 8_000_000:
-        S = 256
-    elif M >= 2_000_000:
-        S = 128
-    elif M >= 600_000:
-        S = 256
-    elif M >= 150_000:
-        S = 64 if out_elems < 40_000 else 32
-    elif M >= 16_384:
-        S = 16
-    else:
-        S = max(1, M // 2048)
-    return max(1, min(S, M // 256))
 
 
 # RT1_SE_DEBUG=1 (tools/dp_gpu_check.py): the fused SE forward keeps copies of (pool, h, gate); the backward flags any
@@ -339,38 +139,12 @@ def gram_bn_preferred(Cin: int, Ce: int, flags: RouteFlags = FLAGS) -> bool:
             and (flags.wgrad_mfma and wgrad_mfma_preferred(1 << 20, Cin, Cin)))
 
 
-def gram_moments(x2d: torch.Tensor):
-    """(G = x^T x fp32 [Cin, Cin], sx = sum_rows x fp32 [Cin]): one pass of the MFMA wgrad kernel that also sums the
-    rows it stages, one fixed-order sum of both partial sets (bindings.cpp gram; ``gram_sx=0``: wgrad + colsum(x))."""
-    if not (FLAGS.gram_sx and FLAGS.wgrad_mfma and wgrad_mfma_preferred(*x2d.shape, x2d.shape[1])):
-        return wgrad(x2d, x2d), _ext().colsum(x2d)
-    x2d = x2d.contiguous()
-    cfg = _WGRAD_TILE.get((x2d.shape[1], x2d.shape[1]))
-    if cfg is None:
-        G, sx = _ext().gram(x2d)
-    else:
-        variant, rows_per_split = cfg
-        G, sx = _ext().gram(x2d, variant, max(1, min(2048, round(x2d.shape[0] / rows_per_split))))
-    return G, sx
-
-
 def gram_bn_consts(x2d: torch.Tensor, We_b: torch.Tensor, bnc: "BNCtx"):
     """Train-mode BN1 constants of y1 = x2d @ We_b^T from x2d alone: G = x^T x and sum x in one MFMA pass, the
     quadratic forms in fp64 (csrc/kernels/xexpand.hip); running stats updated in place."""
     bn = bnc.bn
     return tuple(_ext().x_bn_stats(x2d, We_b, bn.weight, bn.bias, bn.eps, bn.momentum, bn.running_mean,
                                    bn.running_var))
-
-
-def project_gemm(y2: torch.Tensor, Wp_b: torch.Tensor, sc2, sh2, gate, hw: int, bnc: "BNCtx", training: bool,
-                 store_a: bool):
-    """y3 = (silu(bn2(y2)) * gate) @ Wp^T with BN3's batch statistics from the epilogue -> (y3, consts, A|None)."""
-    Ce = y2.shape[-1]
-    M2 = y2.numel() // Ce
-    res = _ext().gemm(y2.view(M2, Ce), Wp_b, False, None, sc2, sh2, gate, hw, stats=training,
-                      cfg=_GEMM_PROJ_TILE[(Ce, Wp_b.shape[0])], store_a=store_a)
-    consts = bnc.train_consts(res[1], res[2], M2) if training else bnc.eval_consts()
-    return res[0], consts, (res[-1] if store_a else None)
 
 
 def _few_splits(part: torch.Tensor) -> torch.Tensor:
@@ -407,9 +181,10 @@ _Z_WIDE_OFF = set()
 @dataclass(frozen=True)
 class BlockRoute:
     """The kernels one MBConv block runs, stage by stage (``plan_block``)."""
-    bn1: str            # BN1 from: "xmode" | "gram" (training) | "gemm" (epilogue or bn_stats) | "input_bn" | "none"
+    # "gemm" / "library" below: the product planner's choice (ops/linear.py plan_product), the statistics with it
+    bn1: str            # BN1 from: "xmode" | "gram" (training) | "gemm" | "input_bn" | "none"
     se: str             # "fused" (se.hip) | "library"
-    proj_fwd: str       # "pw_gemm" (operand prologue) | "gemm_hip" (prologue, contiguous gate) | "library" (bn_apply)
+    proj_fwd: str       # "pw_gemm" (operand prologue) | "gemm_hip" (prologue, contiguous gate) | "library" (after bn_apply)
     proj_bwd: str       # "proj_bwd" (the operand A is not stored) | "stored_a" (wgrad over A + se_bn_bwd_reduce)
     proj_dgrad: str     # "pw_gemm_bnbwd" | "gemm_hip" | "library" (the last two after bn_bwd_apply)
     dw_bwd: str         # "xmode" | "fused" | "unfused" (bn_bwd_apply + dw_bwd_data + dw_bwd_weight)
@@ -520,97 +295,6 @@ def _unopt(t: torch.Tensor) -> Optional[torch.Tensor]:
     return t if t.numel() else None
 
 
-def wgrad(dy: torch.Tensor, x: torch.Tensor, prologue=None, final: bool = False, ok: bool = True,
-          raw: bool = False) -> torch.Tensor:
-    """Weight gradient dy^T @ a for dy [M, Co], x [M, Ci] bf16 -> fp32 [Co, Ci], on the streaming MFMA kernel
-    (csrc/kernels/wgrad.hip).  ``prologue = (scale, shift, gate, act, hw)`` rebuilds a = act(x*scale+shift)*gate
-    inside the kernel (the project conv's input A from y2).  ``final``: the result is a parameter's gradient as is
-    (``ok``: that parameter requires one), so the split-K partial sum may be left to the flat gather
-    (parallel/flat.py defer_partials).  ``raw``: the [splits, Co, Ci] partials themselves, for a consumer kernel
-    that sums them (pw_z_finish)."""
-    ext = _ext()
-    final = final or raw
-    if prologue is not None or (FLAGS.wgrad_mfma and wgrad_mfma_preferred(dy.shape[0], dy.shape[1], x.shape[1])):
-        dy, x = dy.contiguous(), x.contiguous()
-        if prologue is None:
-            cfg = _WGRAD_TILE.get((dy.shape[1], x.shape[1]))
-            if cfg is None:
-                out = ext.wgrad(dy, x, partials=final)
-            else:
-                variant, rows_per_split = cfg
-                out = ext.wgrad(dy, x, variant=variant, splits=max(1, min(2048, round(dy.shape[0] / rows_per_split))),
-                                partials=final)
-        else:
-            sc, sh, gate, act, hw = prologue
-            out = ext.wgrad(dy, x, sc, sh, gate, act, hw, partials=final)
-        if raw:
-            return out
-        return defer_partials(out, ok) if final else out
-    if prologue is not None:
-        raise ValueError("wgrad prologue needs the MFMA kernel (bf16, channels % 8)")
-    return wgrad_bmm(dy, x, final, ok, raw)
-
-
-# (Co, Ci) -> (tile variant of csrc/kernels/wgrad.hip VARIANTS, rows per split) of every plain wgrad call of the step,
-# from the per-site sweep of tools/bench_wgrad_sites.py at 768 frames (profiles/r5_wgrad_sites.log, variant x split
-# count against the automatic pick: the Gram matrix of blocks 19-24 52.0 -> 32.6 us, the 19x19 expand / project
-# gradients 108 / 104 -> 99 / 96 us, block 13's project 157 -> 139 us).  (136, 576) and (232, 816) are the deep
-# shapes where the MFMA kernel beats hipBLASLt's split-K at all (profiles/r2_wgrad_variants.log).
-_WGRAD_TILE = {(136, 576): (1, 2166), (232, 816): (2, 1600)} if switches.on("wgrad_deep") else {}
-_WGRAD_TILE.update({(96, 96): (1, 1083), (136, 136): (1, 2166), (576, 96): (2, 2166), (96, 576): (2, 2166),
-                    (96, 288): (2, 1083), (232, 232): (1, 1200), (64, 512): (1, 600)})
-
-
-def wgrad_mfma_preferred(M: int, Co: int, Ci: int) -> bool:
-    """Shape rule from the per-site sweeps (profiles/r2_wgrad_variants.log, 768 frames at 300x300): the streaming
-    MFMA kernel wins for the mid-resolution layers (Co*Ci <= ~56k, M <= ~5M rows: blocks 2-12, 20-45 % faster) and
-    the two deep shapes of _WGRAD_TILE; hipBLASLt's split-K keeps the very tall skinny ones (blocks 0-1) and the other
-    wide deep ones (14-25: 1.4-2x faster there)."""
-    if Co % 8 or Ci % 8 or M > 5_000_000:
-        return False
-    return Co * Ci <= 56_000 or (Co, Ci) in _WGRAD_TILE
-
-
-# (Co, Ci) -> rows per split of the library split-K weight gradient where the per-site sweep beat _wgrad_splits
-# (tools/bench_wgrad_sites.py --bmm, profiles/r5_wgrad_bmm_sites.log: block 14-17 project 197 -> 170 us at 64 splits,
-# top 156 -> 142 and block-25 expand 204 -> 184 us at 24); the library stays ahead of the MFMA kernel on all of these
-_BMM_ROWS = {(136, 816): 4332, (1536, 384): 3200, (384, 2304): 3200}
-
-
-def wgrad_bmm(dy: torch.Tensor, x: torch.Tensor, final: bool = False, ok: bool = True,
-              raw: bool = False) -> torch.Tensor:
-    """Weight gradient dy^T @ x for dy [M, Co], x [M, Ci] (M = frames*pixels, up to ~1e7 rows).
-
-    A plain TN GEMM here has only (Co/16)*(Ci/16) output tiles (e.g. 18 for
-    144x24) and one workgroup streams all M rows; split-K as a batched GEMM
-    over S row chunks gives S times the parallelism, then an fp32 sum."""
-    M = dy.shape[0]
-    rps = _BMM_ROWS.get((dy.shape[1], x.shape[1]))
-    S = max(1, M // rps) if rps else _wgrad_splits(M, dy.shape[1] * x.shape[1])
-    if S == 1:
-        out = _mm_f32(dy.t(), x)
-        return out[None] if raw else out
-    rows = M // S
-    M1 = rows * S
-    a = dy[:M1].view(S, rows, dy.shape[1]).transpose(1, 2)
-    b = x[:M1].view(S, rows, x.shape[1])
-    try:
-        part = torch.bmm(a, b, out_dtype=torch.float32)
-    except (TypeError, RuntimeError):
-        part = torch.bmm(a, b).float()
-    if M1 < M:                                # the leftover rows join the first split
-        part[0] += _mm_f32(dy[M1:].t(), x[M1:])
-    if raw:
-        return part.contiguous()
-    if final:
-        return defer_partials(part.contiguous(), ok)
-    return _ext().colsum(part)                # deterministic fixed-order sum (csrc/kernels/reduce.hip)
-
-
-def _partials(M: int) -> int:
-    return int(max(1, min(1024, (M + 255) // 256)))
-
-
 class BNCtx:
     """Per-BN bookkeeping shared by forward and backward (not a tensor)."""
 
@@ -629,15 +313,6 @@ class BNCtx:
         sc = bn.weight.float() * rstd
         sh = bn.bias.float() - bn.running_mean.float() * sc
         return sc.contiguous(), sh.contiguous(), bn.running_mean.float().contiguous(), rstd.contiguous()
-
-
-def _bn_train_or_eval(bnc: BNCtx, training: bool, y2d: torch.Tensor = None, partials=None):
-    if training:
-        if partials is None:
-            partials = _ext().bn_stats(y2d, _partials(y2d.shape[0]))
-        count = y2d.shape[0] if y2d is not None else None
-        return bnc.train_consts(partials[0], partials[1], count)
-    return bnc.eval_consts()
 
 
 class StemFn(torch.autograd.Function):
@@ -727,13 +402,13 @@ class MBConvFn(torch.autograd.Function):
             # y1 = x @ We^T is never materialised: BN1 from x's Gram matrix, y1 rebuilt in dw_fwd_x
             sc1, sh1, mu1, rs1 = (gram_bn_consts(x.view(M, Cin), We_b, bns[0]) if training else bns[0].eval_consts())
         elif bn1 == "gram":
-            y1 = _lin(x.view(M, Cin), We_b).view(N, H, W, Ce)
+            y1 = lin(x.view(M, Cin), We_b).view(N, H, W, Ce)
             gram = gram_moments(x.view(M, Cin))
             bn = bns[0].bn
             sc1, sh1, mu1, rs1 = ext.bn_from_gram(gram[0], gram[1], We_b, float(M), bn.weight, bn.bias, bn.eps,
                                                   bn.momentum, bn.running_mean, bn.running_var)
         elif bn1 == "gemm":
-            y1, (sc1, sh1, mu1, rs1) = _lin_bn(x.view(M, Cin), We_b, bns[0], training)
+            y1, (sc1, sh1, mu1, rs1), _ = lin_bn(x.view(M, Cin), We_b, bns[0], training)
             y1 = y1.view(N, H, W, Ce)
         elif bn1 == "input_bn":
             if spec.has_skip:
@@ -775,14 +450,16 @@ class MBConvFn(torch.autograd.Function):
         need_a = training or Wp.requires_grad or x.requires_grad
         proj = "library" if (r.proj_fwd == "gemm_hip" and not gate.is_contiguous()) else r.proj_fwd
         if proj == "pw_gemm":
-            y3, (sc3, sh3, mu3, rs3), A = _lin_bn(y2.view(M2, Ce), _bf(Wp).reshape(Cout, Ce), bn3, training,
-                                                  pro=(sc2, sh2, gate, HW2, need_a and r.proj_bwd != "proj_bwd"))
+            y3, (sc3, sh3, mu3, rs3), A = lin_bn(y2.view(M2, Ce), _bf(Wp).reshape(Cout, Ce), bn3, training,
+                                                 pro=(sc2, sh2, gate, HW2, need_a and r.proj_bwd != "proj_bwd"))
         elif proj == "gemm_hip":
-            y3, (sc3, sh3, mu3, rs3), A = project_gemm(y2, _bf(Wp).reshape(Cout, Ce).contiguous(), sc2, sh2, gate,
-                                                       HW2, bn3, training, need_a)
+            # gemm.hip with the same prologue and BN3's statistics from its epilogue
+            plan = Product("gemm_hip", _GEMM_PROJ_TILE[(Ce, Cout)], "epilogue" if training else "none")
+            y3, (sc3, sh3, mu3, rs3), A = lin_bn(y2.view(M2, Ce), _bf(Wp).reshape(Cout, Ce).contiguous(), bn3, training,
+                                                 pro=(sc2, sh2, gate, HW2, need_a), plan=plan)
         else:
             A = ext.bn_apply(y2, sc2, sh2, ACT_SILU, gate, HW2)                 # [N, H2, W2, Ce]
-            y3, (sc3, sh3, mu3, rs3) = _lin_bn(A.view(M2, Ce), _bf(Wp).reshape(Cout, Ce), bn3, training)
+            y3, (sc3, sh3, mu3, rs3), _ = lin_bn(A.view(M2, Ce), _bf(Wp).reshape(Cout, Ce), bn3, training)
         skip = x if spec.has_skip else None
         keep_t = keep if (keep is not None and spec.has_skip) else None
         out = ext.block_tail(y3.view(N, HW2, Cout), sc3, sh3, keep_t, skip.view(N, HW2, Cout) if skip is not None
@@ -829,7 +506,7 @@ class MBConvFn(torch.autograd.Function):
             if r.proj_dgrad == "gemm_hip":
                 dA = ext.gemm(dy3.view(M2, Cout), Wp2.contiguous(), True, cfg=_GEMM_PROJ_DGRAD_TILE[(Ce, Cout)])[0]
             else:
-                dA = _lin(dy3, Wp2.t())                                          # [M2, Ce]
+                dA = lin(dy3, Wp2.t())                                           # [M2, Ce]
         # ---- project weight gradient, squeeze-excitation + BN2 backward statistics
         if A is None and r.proj_bwd == "proj_bwd":
             # SE + BN2 backward sums and dWp from (dy3, y2) in one pass per frame, the dA-weighted sums contracted
@@ -897,7 +574,7 @@ class MBConvFn(torch.autograd.Function):
             mdz1, mdzx1, dg1, db1 = ext.bn_bwd_finalize_new(bn1p[0], bn1p[1], float(M))
             dy1 = ext.bn_bwd_apply(d1, None, None, 0, y1, sc1, sh1, mu1, rs1, g1.float().contiguous(), ACT_SILU,
                                    mdz1, mdzx1).view(M, Ce)
-            dx = _lin(dy1, _bf(We).reshape(Ce, Cin).t()).view(N, H, W, Cin)
+            dx = lin(dy1, _bf(We).reshape(Ce, Cin).t()).view(N, H, W, Cin)
             dWe = wgrad(dy1, x.view(M, Cin), final=True, ok=ctx.needs_input_grad[4]).view_as(We)
         elif r.expand_bwd != "none":
             # SiLU/BN1 backward + dgrad + wgrad of the expand conv in ONE pass; the five per-channel constants come
@@ -974,9 +651,9 @@ class TopFn(torch.autograd.Function):
         Ct, E = Wt.shape[0], W1.shape[0]
         M = N * H * W
         # BN statistics from the wide GEMM's epilogue (no bn_stats pass over the 1536-wide y)
-        y, (sc, sh, mu, rs) = _lin_bn(x.view(M, Cin), _bf(Wt).reshape(Ct, Cin), bnc, training)
+        y, (sc, sh, mu, rs), _ = lin_bn(x.view(M, Cin), _bf(Wt).reshape(Ct, Cin), bnc, training)
         a = ext.bn_apply(y, sc, sh, ACT_SILU, None, 0)
-        f = _lin(a, _bf(W1).reshape(E, Ct))        # [M, E]
+        f = lin(a, _bf(W1).reshape(E, Ct))         # [M, E]
         ones, zeros = _ones_zeros(E, x.device)
         out = ext.block_tail(f.view(N, H * W, E), ones, zeros, None, None, fmul, fadd)
         ctx.save_for_backward(x, Wt, gt, W1, fmul, y, a, f, sc, sh, mu, rs)
@@ -1000,12 +677,12 @@ class TopFn(torch.autograd.Function):
         df = ext.block_tail(dout.view(N, HW, E), ones, zeros, None, None, fmul.float().contiguous(), zeros_ne).view(M, E)
         W1m = _bf(W1).reshape(E, Ct)
         dW1 = wgrad(df, a, final=True, ok=ctx.needs_input_grad[4]).view_as(W1)
-        da = _lin(df, W1m.t())                                                   # [M, Ct]
+        da = lin(df, W1m.t())                                                    # [M, Ct]
         pa, pb = ext.bn_bwd_reduce(da, None, None, 0, y, sc, sh, mu, rs, ACT_SILU, _partials(M))
         mdz, mdzx, dg, db = ext.bn_bwd_finalize_new(pa, pb, float(M))
         dy = ext.bn_bwd_apply(da, None, None, 0, y, sc, sh, mu, rs, gt.float().contiguous(), ACT_SILU, mdz, mdzx)
         dWt = wgrad(dy, x.view(M, Cin), final=True, ok=ctx.needs_input_grad[1]).view_as(Wt)
-        dx = _lin(dy, _bf(Wt).reshape(Ct, Cin).t()).view(N, H, W, Cin)
+        dx = lin(dy, _bf(Wt).reshape(Ct, Cin).t()).view(N, H, W, Cin)
         return dx, dWt, dg, db, dW1, dmul, dadd, None, None
 
 

@@ -2,7 +2,7 @@
 
 ``x = tokens @ W^T + b + pos[:S]`` as ONE MFMA kernel with a bias + position-row epilogue that writes the fp32
 residual stream directly (``csrc/kernels/pwtall.hip``, ``rt1_embed_fwd``), replacing a bf16 GEMM, a position add
-and an fp32 up-cast.  Backward: dX through the transformer's data-gradient route (attention._proj), dW on the MFMA
+and an fp32 up-cast.  Backward: dX through the transformer's data-gradient route (linear.proj), dW on the MFMA
 wgrad kernel (bf16 operands, fp32 dW), db / dpos as row reductions.
 """
 from __future__ import annotations
@@ -10,7 +10,7 @@ from __future__ import annotations
 import torch
 
 from ._ext import load as _ext
-from .attention import _proj, _wgrad
+from .linear import _bf, proj, token_wgrad
 
 BF = torch.bfloat16
 
@@ -18,7 +18,6 @@ BF = torch.bfloat16
 class EmbedFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, tokens, w, b, pos):
-        from .backbone import _bf
         B, S, K = tokens.shape
         x = tokens.to(BF).contiguous()
         wb = _bf(w).contiguous()
@@ -34,10 +33,10 @@ class EmbedFn(torch.autograd.Function):
         N = wb.shape[0]
         g2 = g.reshape(B * S, N)
         gb = g2.to(BF)
-        dx = _proj(gb, wb, True).view(B, S, K).to(tdt) if ctx.needs_input_grad[0] else None
+        dx = proj(gb, wb, True).view(B, S, K).to(tdt) if ctx.needs_input_grad[0] else None
         # dW on the streaming MFMA wgrad kernel with the transformer's short-reduction split (hipBLASLt ran this
         # [512, 8448] x [8448, 512] TN product at 64 us, ~5 % of its roofline: tools/gemm_census.py)
-        dw = _wgrad(gb, x.view(B * S, K), True) if ctx.needs_input_grad[1] else None
+        dw = token_wgrad(gb, x.view(B * S, K), True) if ctx.needs_input_grad[1] else None
         db = _ext().colsum(g2) if ctx.needs_input_grad[2] else None
         dpos = None
         if ctx.needs_input_grad[3]:

@@ -94,10 +94,10 @@ class FusedRT1:
         return {ws[0].data_ptr(): (W, b)}
 
     def _refresh_shadow(self):
-        from . import backbone
+        from . import backbone, linear
         if self._flat is None:
             from . import attention
-            backbone.set_weight_shadow(None)
+            linear.set_weight_shadow(None)
             backbone.set_film_packs({})
             attention.set_qkv_packs({})
             return
@@ -105,7 +105,7 @@ class FusedRT1:
         if self._qkv_copy is not None:
             from ._ext import load
             load().multi_copy_(*self._qkv_copy)
-        backbone.set_weight_shadow(self._views)
+        linear.set_weight_shadow(self._views)
         backbone.set_film_packs(self._film_packs)
         # re-installed every forward, like the weight shadow: another FusedRT1 (an eval model in the same process)
         # may have replaced the module-global packs since this model's attach_flat

@@ -15,7 +15,7 @@ from __future__ import annotations
 import torch
 
 from ._ext import load
-from .attention import _wgrad
+from .linear import _bf, token_wgrad
 
 BF = torch.bfloat16
 
@@ -26,7 +26,6 @@ class HeadCEFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, hidden, W, bias, positions, targets, label_smoothing=0.0, z_loss=0.0):
-        from .backbone import _bf
         ext = load()
         h = hidden.float().contiguous()
         Wb = _bf(W).contiguous()
@@ -51,7 +50,7 @@ class HeadCEFn(torch.autograd.Function):
         B, S, E = ctx.shape
         dz = load().head_ce_scale(G, dce.float().contiguous())             # [R, V] bf16
         dh = torch.mm(dz, Wb)                                               # [R, E]
-        dW = _wgrad(dz, hb, True, ctx.needs_input_grad[1])                                                 # [V, E] fp32, MFMA wgrad kernel
+        dW = token_wgrad(dz, hb, True, ctx.needs_input_grad[1])           # [V, E] fp32, MFMA wgrad kernel
         db = load().colsum(dz)
         dhidden = torch.zeros(B, S, E, device=G.device, dtype=torch.float32)
         dhidden[:, positions.long()] = dh.view(B, -1, E).float()           # positions are unique

@@ -17,7 +17,7 @@ import os
 from typing import Dict
 
 DEFAULTS: Dict[str, str] = {
-    # backbone (ops/backbone.py)
+    # backbone (ops/backbone.py; RouteFlags and the GEMM / weight-gradient planners in ops/linear.py)
     "pw_tall": "1",        # tall-skinny MFMA kernel for wide-K narrow-N 1x1 convs (0: hipBLASLt)
     "g256": "1",           # top / block-25 expand on gemm256.hip with the BN-statistics epilogue
     "wgrad_mfma": "1",     # streaming MFMA weight-gradient kernel on the mid-resolution shapes
@@ -39,10 +39,10 @@ DEFAULTS: Dict[str, str] = {
     "gemm_proj": "1",      # deep project convs on gemm.hip with prologue and BN3-statistics epilogue
     "gemm_proj_dgrad": "1",  # ... and their data gradients
     "tall_res": "1",       # residual gradient in the wide dz-mode dgrad's epilogue
-    "gram_sx": "1",        # x's column sums from the Gram-matrix wgrad pass (ops/backbone.py gram_moments)
+    "gram_sx": "1",        # x's column sums from the Gram-matrix wgrad pass (ops/linear.py gram_moments)
     # transformer (ops/attention.py)
     "tf_wgrad": "1",       # transformer weight gradients on the MFMA wgrad kernel
-    "tf_gemm": "1",        # transformer projections of ops/attention.py _TF_GEMM_CFG on gemm.hip's small tiles
+    "tf_gemm": "1",        # transformer projections of ops/linear.py _TF_GEMM_CFG on gemm.hip's small tiles
     "tf_fuse_ln": "1",     # next LayerNorm formed in the residual kernel, LN2 backward emits the bf16 operand
     # data parallel (parallel/flat.py)
     "multi_copy": "1",     # one-launch gradient gather into the flat bucket

@@ -11,6 +11,7 @@ from __future__ import annotations
 import torch
 
 from ._ext import load
+from .linear import _bf, wgrad
 
 BF = torch.bfloat16
 
@@ -18,7 +19,6 @@ BF = torch.bfloat16
 class TokenLearnerFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, feats, ln_w, ln_b, w1, b1, w2, b2, eps: float, want_maps: bool = False):
-        from .backbone import _bf
         ext = load()
         x = feats.to(BF).contiguous()
         W1 = _bf(w1).reshape(64, 512).contiguous()
@@ -35,7 +35,6 @@ class TokenLearnerFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout, *_):
-        from .backbone import wgrad
         x, mu, rs, z1, s, ln_w, ln_b, W1, W2 = ctx.saved_tensors
         w1_shape, w2_shape = ctx.shapes
         dx, dz1, xn, pw2, pg = load().tl_bwd(x, dout.to(BF).contiguous(), s, z1, mu, rs, ln_w.float().contiguous(),

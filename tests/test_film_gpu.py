@@ -96,7 +96,7 @@ def test_film_fn_gradients_reach_every_projection(ext):
                                                     (1000, 136, 816, 5, 3)])
 def test_wgrad_column_sums(ext, M, Co, Ci, variant, splits):
     """wgrad(sums=True): each split's dW partial followed by the column sums of dy (the bias gradient) -- the
-    transformer's fused Q/K/V dW + db (ops/attention.py _wgrad_bias) -- vs fp32 torch, and the same dW as without."""
+    transformer's fused Q/K/V dW + db (ops/linear.py token_wgrad, bias=True) -- vs fp32 torch, and the same dW as without."""
     torch.manual_seed(M + Co)
     dy = torch.randn(M, Co, device="cuda").to(BF)
     x = torch.randn(M, Ci, device="cuda").to(BF)

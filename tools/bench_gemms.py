@@ -3,8 +3,7 @@
 against the HBM / MFMA roofline of each shape.
 
 For every MBConv expand/project conv of FiLM-EfficientNet-B3 at --frames x --res, times (HIP events,
-median) the forward GEMM, the backward-data GEMM and the split-K weight-gradient GEMM exactly as
-``ops/backbone.py`` issues them.
+median) the forward GEMM, the backward-data GEMM and the weight gradient as ``ops/linear.py`` plans it.
 
   python tools/bench_gemms.py --frames 768 --res 300 [--use-ext]
 """
@@ -18,7 +17,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pytorch_rt1_for_distributed_training_amd.models.efficientnet import block_specs, conv_out_size  # noqa: E402
-from pytorch_rt1_for_distributed_training_amd.ops import backbone as bb  # noqa: E402
+from pytorch_rt1_for_distributed_training_amd.ops import linear  # noqa: E402
 
 BF = torch.bfloat16
 HBM = 5.5e12      # sustained bytes/s used for the roofline
@@ -50,7 +49,7 @@ def main():
     ap.add_argument("--frames", type=int, default=768)
     ap.add_argument("--res", type=int, default=300)
     ap.add_argument("--iters", type=int, default=10)
-    ap.add_argument("--use-ext", action="store_true", help="time the HIP GEMM path of ops.backbone when present")
+    ap.add_argument("--use-ext", action="store_true", help="time the HIP GEMM path of ops.linear when present")
     a = ap.parse_args()
     N = a.frames
     H = W = conv_out_size(a.res, 3, 2)
@@ -68,9 +67,9 @@ def main():
             w = (torch.randn(Nn, K, device="cuda") * 0.1).to(BF)
             dy = torch.randn(M, Nn, device="cuda").to(BF)
             wt = w.t()
-            t_f = timeit(lambda: bb._mm(x, wt), a.iters)
-            t_d = timeit(lambda: bb._mm(dy, w), a.iters)
-            t_w = timeit(lambda: bb.wgrad(dy, x), a.iters)
+            t_f = timeit(lambda: torch.mm(x, wt), a.iters)
+            t_d = timeit(lambda: torch.mm(dy, w), a.iters)
+            t_w = timeit(lambda: linear.wgrad(dy, x), a.iters)
             r_f, r_d = roof_us(M, K, Nn), roof_us(M, Nn, K)
             if a.use_ext:
                 from pytorch_rt1_for_distributed_training_amd.ops import load

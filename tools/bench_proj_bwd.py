@@ -15,7 +15,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pytorch_rt1_for_distributed_training_amd.models.efficientnet import block_specs, conv_out_size  # noqa: E402
-from pytorch_rt1_for_distributed_training_amd.ops import backbone, load  # noqa: E402
+from pytorch_rt1_for_distributed_training_amd.ops import backbone, linear, load  # noqa: E402
 
 
 def timeit(fn, iters=10):
@@ -57,7 +57,7 @@ def main():
         Wp = (torch.randn(Cout, Ce, device="cuda") * 0.1).to(torch.bfloat16)
         gate = torch.rand(N, Ce, device="cuda")
         sc, sh, mu, rs = (torch.rand(Ce, device="cuda") + 0.5 for _ in range(4))
-        t_old = timeit(lambda: (backbone.wgrad(dy3, A), ext.se_bn_bwd_reduce(dA.view(N, HW, Ce), y2.view(N, HW, Ce),
+        t_old = timeit(lambda: (linear.wgrad(dy3, A), ext.se_bn_bwd_reduce(dA.view(N, HW, Ce), y2.view(N, HW, Ce),
                                                                              sc, sh, mu, rs)))
         t_new = timeit(lambda: ext.proj_bwd(dy3, y2.view(N, HW, Ce), Wp, gate, sc, sh, mu, rs))
         gbs = M * (Ce + Cout) * 2 / t_new / 1e3

@@ -16,7 +16,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pytorch_rt1_for_distributed_training_amd.models.efficientnet import block_specs, conv_out_size  # noqa: E402
-from pytorch_rt1_for_distributed_training_amd.ops import backbone, load  # noqa: E402
+from pytorch_rt1_for_distributed_training_amd.ops import backbone, linear, load  # noqa: E402
 from tools.bench_dw_phases import timeit  # noqa: E402
 
 BF = torch.bfloat16
@@ -70,8 +70,8 @@ def main():
             # the weight gradient dWp = dy3^T A: on the stored A, or with A rebuilt from y2 in the wgrad kernel
             dy3 = torch.randn(M2, Co, device=dev).to(BF)
             t_store = timeit(lambda: ext.pw_tall(y2, wp, sc, sh, gate, HW2, True), a.iters)
-            t_wg = timeit(lambda: backbone.wgrad(dy3, A), a.iters)
-            t_wgp = timeit(lambda: backbone.wgrad(dy3, y2, prologue=(sc, sh, gate, ACT_SILU, HW2)), a.iters)
+            t_wg = timeit(lambda: linear.wgrad(dy3, A), a.iters)
+            t_wgp = timeit(lambda: linear.wgrad(dy3, y2, prologue=(sc, sh, gate, ACT_SILU, HW2)), a.iters)
             extra = (f" | pro+store {t_store:6.1f}  wgrad(A) {t_wg:6.1f}  wgrad(pro) {t_wgp:6.1f} | now "
                      f"{t_apply + t_plain + t_wg:6.1f}  pro+store {t_store + t_wg:6.1f}  pro+wgrad(pro) "
                      f"{t_pro + t_wgp:6.1f}")

@@ -15,7 +15,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pytorch_rt1_for_distributed_training_amd.models.efficientnet import block_specs, conv_out_size  # noqa: E402
-from pytorch_rt1_for_distributed_training_amd.ops import backbone, load  # noqa: E402
+from pytorch_rt1_for_distributed_training_amd.ops import linear, load  # noqa: E402
 
 BF = torch.bfloat16
 
@@ -65,8 +65,8 @@ def main():
         f_u = timeit(lambda: ext.pw_gemm(ext.bn_apply(y2, sc, sh, 1, gate, hw), wp, 2048, True))
         f_p = timeit(lambda: ext.pw_gemm(y2, wp, 2048, True, sc, sh, gate, hw))
         f_s = timeit(lambda: ext.pw_gemm(y2, wp, 2048, True, sc, sh, gate, hw, True))
-        w_u = timeit(lambda: backbone.wgrad(dy3, A))
-        w_p = timeit(lambda: backbone.wgrad(dy3, y2, prologue=(sc, sh, gate, 1, hw)))
+        w_u = timeit(lambda: linear.wgrad(dy3, A))
+        w_p = timeit(lambda: linear.wgrad(dy3, y2, prologue=(sc, sh, gate, 1, hw)))
         fs_tot[0] += f_s + w_u
         tu += f_u + w_u
         tp += f_p + w_p

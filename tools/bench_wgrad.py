@@ -7,6 +7,7 @@ vs the previous split-K torch.bmm (hipBLASLt) + column-sum path, per shape (medi
 from __future__ import annotations
 
 import argparse
+import dataclasses
 import os
 import sys
 
@@ -14,7 +15,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pytorch_rt1_for_distributed_training_amd.models.efficientnet import block_specs, conv_out_size  # noqa: E402
-from pytorch_rt1_for_distributed_training_amd.ops import backbone, load  # noqa: E402
+from pytorch_rt1_for_distributed_training_amd.ops import linear, load  # noqa: E402
 
 
 def timeit(fn, iters=10):
@@ -38,6 +39,11 @@ def main():
     ap.add_argument("--variants", action="store_true", help="also time every tile variant of the MFMA kernel")
     a = ap.parse_args()
     ext = load()
+    library = dataclasses.replace(linear.FLAGS, wgrad_mfma=False)      # the split-K bmm / mm plans
+
+    def library_wgrad(dy, x):
+        return linear.wgrad(dy, x, plan=linear.plan_wgrad(dy.shape[0], dy.shape[1], x.shape[1], library))
+
     N = a.frames
     H = W = conv_out_size(a.res, 3, 2)
     shapes = []
@@ -55,14 +61,14 @@ def main():
     for name, M, Co, Ci in shapes:
         dy = torch.randn(M, Co, device="cuda").to(torch.bfloat16)
         x = torch.randn(M, Ci, device="cuda").to(torch.bfloat16)
-        t_old = timeit(lambda: backbone.wgrad_bmm(dy, x))
+        t_old = timeit(lambda: library_wgrad(dy, x))
         t_new = timeit(lambda: ext.wgrad(dy, x))
         tot_old += t_old
         tot_new += t_new
         gbs = (M * (Co + Ci) * 2) / t_new / 1e3
         vs = ""
         if a.variants:
-            ref = backbone.wgrad_bmm(dy, x)
+            ref = library_wgrad(dy, x)
             for v in range(NV):
                 out = ext.wgrad(dy, x, variant=v)
                 err = (out - ref).abs().max().item() / max(ref.abs().max().item(), 1e-6)
