@@ -25,6 +25,8 @@ import sys
 
 
 LR_SCHEDULES = ("constant", "linear", "cosine", "rsqrt")
+PHOTOMETRIC_NEEDS_SHARD = ("--photometric runs on the GPU decode path and needs the packed-shard format "
+                           "(tools/pack_shards.py): .npz episodes and --synthetic decode on CPU workers")
 DEFAULT_MILESTONES = [50, 75, 90]
 
 
@@ -144,7 +146,38 @@ def build_parser() -> argparse.ArgumentParser:
                         "step; 'auto' = hbm on GPU when the rank's frames fit --hbm_data_gb")
     p.add_argument("--hbm_data_gb", type=float, default=96.0,
                    help="HBM budget per rank for resident training frames (of 288 GB per MI355X)")
+    p.add_argument("--photometric", action="store_true",
+                   help="colour augmentation of the training frames on the GPU decode path (packed shards only; one "
+                        "draw per window; validation and test never get it): brightness +-0.1, saturation x[0.8, "
+                        "1.2], hue +-0.03 turns, contrast x[0.8, 1.2] unless the flags below say otherwise")
+    p.add_argument("--photometric_brightness", type=float, default=None, metavar="D",
+                   help="brightness delta drawn in [-D, D] (0 <= D <= 1)")
+    p.add_argument("--photometric_saturation", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                   help="saturation factor drawn in [LO, HI] (0 <= LO <= HI)")
+    p.add_argument("--photometric_hue", type=float, default=None, metavar="D",
+                   help="hue delta in turns drawn in [-D, D] (0 <= D <= 0.5)")
+    p.add_argument("--photometric_contrast", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                   help="contrast factor drawn in [LO, HI] (0 <= LO <= HI)")
     return p
+
+
+def photometric_spec(args):
+    """The ``PhotometricDistortions`` range spec the --photometric flags ask for (None: off).  Raises ValueError on a
+    range the transform has no meaning for."""
+    if not getattr(args, "photometric", False):
+        return None
+    from pytorch_rt1_for_distributed_training_amd.data.augment import PhotometricDistortions
+    from pytorch_rt1_for_distributed_training_amd.data.photometric import check_spec
+    spec = PhotometricDistortions()
+    if args.photometric_brightness is not None:
+        spec.brightness_max_delta = args.photometric_brightness
+    if args.photometric_saturation is not None:
+        spec.saturation_lower, spec.saturation_upper = args.photometric_saturation
+    if args.photometric_hue is not None:
+        spec.hue_max_delta = args.photometric_hue
+    if args.photometric_contrast is not None:
+        spec.contrast_lower, spec.contrast_upper = args.photometric_contrast
+    return check_spec(spec)
 
 
 def _spawn_local(args) -> int:
@@ -186,11 +219,14 @@ def make_loaders(args, cfg, ctx):
             return D.ShardBatchLoader(os.path.join(root, split), bs, cfg.seq_len, args.random_crop_factor,
                                       shuffle=shuffle, rank=ctx.rank, world=ctx.world_size, seed=args.seed,
                                       drop_last=shuffle, threads=max(2, min(args.num_workers, 16)),
-                                      pin=ctx.device.type == "cuda")
+                                      pin=ctx.device.type == "cuda",
+                                      photometric=photometric_spec(args) if split == "train" else None)
         train = _resident_train_loader(args, cfg, ctx, os.path.join(root, "train"))
         if train is None:
             train = shard("train", True, args.batch_size)
         return train, shard("test", False, args.batch_size), shard("val", False, args.batch_size)
+    if getattr(args, "photometric", False):
+        raise SystemExit(PHOTOMETRIC_NEEDS_SHARD)
     tf = D.DecodeAndRandomResizedCrop(args.random_crop_factor, (args.width, args.height), as_uint8=True)
     for split in ("train", "test", "val"):
         if not os.path.isdir(os.path.join(root, split)):
@@ -231,7 +267,7 @@ def _resident_train_loader(args, cfg, ctx, path):
         print(f"[data] resident training frames: {res.frames.shape[0]} frames, {res.nbytes / 2 ** 30:.2f} GB per rank, "
               f"loaded in {res.load_s:.1f} s", flush=True)
     return R.ResidentBatchLoader(res, args.batch_size, cfg.seq_len, args.random_crop_factor, shuffle=True,
-                                 seed=args.seed, drop_last=True)
+                                 seed=args.seed, drop_last=True, photometric=photometric_spec(args))
 
 
 def _batch_transform(train_loader, cfg):
@@ -290,6 +326,12 @@ def train(args):
             print(f"[train] lr_schedule {lr_schedule}, milestones {resolve_milestones(args)}", flush=True)
         if args.ema_decay > 0:
             print(f"[train] ema_decay {args.ema_decay} (warm-up {'off' if args.no_ema_warmup else 'on'})", flush=True)
+        if args.photometric:
+            ps = photometric_spec(args)
+            print(f"[train] photometric brightness +-{ps.brightness_max_delta:g}, saturation "
+                  f"[{ps.saturation_lower:g}, {ps.saturation_upper:g}], hue +-{ps.hue_max_delta:g} turns, contrast "
+                  f"[{ps.contrast_lower:g}, {ps.contrast_upper:g}] (one draw per window, training frames only)",
+                  flush=True)
         if args.label_smoothing or args.z_loss or args.token_accuracy:
             print(f"[train] label_smoothing {args.label_smoothing:g}, z_loss {args.z_loss:g} (training mode only: "
                   f"eval_loss / test_loss stay the plain CE), token_accuracy {'on' if args.token_accuracy else 'off'}",
@@ -373,6 +415,17 @@ def check_args(parser, args):
                      f"({args.warmup_steps}) for --lr_schedule {args.lr_schedule}")
     if args.lr_schedule == "none" and (args.warmup_steps or args.lr_decay_steps or args.min_lr_ratio):
         parser.error("--warmup_steps / --lr_decay_steps / --min_lr_ratio need --lr_schedule")
+    ranges = (args.photometric_brightness, args.photometric_saturation, args.photometric_hue,
+              args.photometric_contrast)
+    if not args.photometric and any(v is not None for v in ranges):
+        parser.error("--photometric_brightness / _saturation / _hue / _contrast need --photometric")
+    if args.photometric:
+        if args.synthetic or args.data_format == "npz":
+            parser.error(PHOTOMETRIC_NEEDS_SHARD)
+        try:
+            photometric_spec(args)
+        except ValueError as e:
+            parser.error(str(e))
 
 
 def main(argv=None):

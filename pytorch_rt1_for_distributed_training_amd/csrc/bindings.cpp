@@ -432,6 +432,26 @@ at::Tensor crop_resize_gather_u8(at::Tensor raw, at::Tensor rows, at::Tensor box
     return out;
 }
 
+// photometric augmentation in place on decoded frames: image [N, 3, H, W] or [B, T, 3, H, W] uint8, params
+// [N / frames_per_window, 4] fp32 (brightness delta, saturation factor, hue delta in turns, contrast factor)
+void photometric_u8_(at::Tensor image, at::Tensor params, int64_t frames_per_window) {
+    TORCH_CHECK(image.is_cuda() && image.is_contiguous() && image.scalar_type() == at::kByte &&
+                (image.dim() == 4 || image.dim() == 5) && image.size(image.dim() - 3) == 3,
+                "photometric_u8_: image must be a contiguous [N, 3, H, W] or [B, T, 3, H, W] uint8 GPU tensor");
+    const int64_t N = image.dim() == 4 ? image.size(0) : image.size(0) * image.size(1);
+    const int64_t HW = image.size(image.dim() - 2) * image.size(image.dim() - 1);
+    TORCH_CHECK(frames_per_window > 0 && N % frames_per_window == 0, "photometric_u8_: ", N,
+                " frames are not a whole number of windows of ", frames_per_window);
+    TORCH_CHECK(params.is_cuda() && params.device() == image.device() && params.is_contiguous() &&
+                params.scalar_type() == at::kFloat && params.dim() == 2 && params.size(0) == N / frames_per_window &&
+                params.size(1) == 4, "photometric_u8_: params must be fp32 [", N / frames_per_window,
+                ", 4] on the image's device");
+    if (N == 0 || HW == 0) return;
+    TORCH_CHECK(N <= INT32_MAX && 3 * HW <= INT32_MAX, "photometric_u8_: batch or frame too large");
+    check_launch(rt1_photometric_u8(image.data_ptr<uint8_t>(), params.data_ptr<float>(), (int)N,
+                                    (int)frames_per_window, (int)HW, cur_stream()), "photometric_u8_");
+}
+
 Bf* bp(const at::Tensor& t) { return reinterpret_cast<Bf*>(t.data_ptr()); }
 const Bf* bpo(const OptT& t) { return t.has_value() && t->defined() ? reinterpret_cast<const Bf*>(t->data_ptr()) : nullptr; }
 const float* fpo(const OptT& t) { return t.has_value() && t->defined() ? t->data_ptr<float>() : nullptr; }
@@ -1639,6 +1659,8 @@ PYBIND11_MODULE(_rt1_hip, m) {
     m.def("crop_resize_u8", &crop_resize_u8, "Pillow-exact random-resized-crop of raw uint8 frames (GPU)");
     m.def("crop_resize_gather_u8", &crop_resize_gather_u8,
           "crop_resize_u8 over frames gathered by index from an HBM-resident [F, h, w, 3] table");
+    m.def("photometric_u8_", &photometric_u8_,
+          "brightness / saturation / hue / contrast of planar uint8 frames in place, one parameter row per window");
     m.def("multi_reduce_copy_", &multi_reduce_copy_, "dst[i] = fixed-order sum of splits[i] partials of src[i]",
           py::arg("dst"), py::arg("src"), py::arg("splits"), py::arg("sstride"));
     m.def("multi_copy_", &multi_copy_, "dst[i].copy_(src[i]) for many same-dtype tensors, 128 per launch");

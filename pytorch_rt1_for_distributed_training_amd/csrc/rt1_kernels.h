@@ -280,6 +280,10 @@ int rt1_crop_resize_u8(const uint8_t* raw, const int* boxes, int N, int h, int w
 int rt1_crop_resize_gather_u8(const uint8_t* raw, int64_t F, const int64_t* rows, const int* boxes, int N, int h,
                               int w, int H, int W, uint8_t* out, hipStream_t st);
 
+// photometric.hip (brightness / saturation / hue / contrast of planar uint8 frames [N, 3, HW], in place; params
+// [N / T, 4] fp32 (db, fs, dh, fc) shared by the T frames of a window; one workgroup per frame)
+int rt1_photometric_u8(uint8_t* img, const float* params, int N, int T, int HW, hipStream_t st);
+
 // wgrad.hip (1x1-conv weight gradient on MFMA, split over pixels, optional BN/act/gate prologue on a)
 int rt1_wgrad_splits(int64_t M, int Co, int Ci, int variant);   // variant < 0: the built-in tile pick
 int rt1_wgrad_run(const rt1_bf16* dy, const rt1_bf16* a, int64_t M, int Co, int Ci, const float* scale,

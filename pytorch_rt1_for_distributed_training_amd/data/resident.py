@@ -35,6 +35,7 @@ from typing import Dict, Iterator, List, Optional, Tuple
 import numpy as np
 import torch
 
+from .photometric import apply_to_decoded, check_spec, photometric_generator, photometric_params
 from .shards import Shard, crop_boxes, _pil_crop_resize, gpu_crop_supported
 
 
@@ -190,11 +191,15 @@ class ResidentShard:
 
 class ResidentBatchLoader:
     """Per-batch plans over a :class:`ResidentShard`: ``{"plan_rows": [B, T] int64, "crop_boxes": [B, T, 4] int32}``
-    (pinned when CUDA is present); :func:`decode_resident` turns a plan into the model's batch on the device."""
+    (pinned when CUDA is present); :func:`decode_resident` turns a plan into the model's batch on the device.
+    ``photometric`` (a ``data.augment.PhotometricDistortions`` range spec, training only) adds ``"photometric"``
+    [B, 4] fp32 to every plan: one (db, fs, dh, fc) row per window (data/photometric.py)."""
 
     def __init__(self, resident: ResidentShard, batch_size: int, seq_len: int, crop_factor: Optional[float] = 0.95,
-                 shuffle: bool = True, seed: int = 0, drop_last: bool = True, pin: Optional[bool] = None):
+                 shuffle: bool = True, seed: int = 0, drop_last: bool = True, pin: Optional[bool] = None,
+                 photometric=None):
         self.res = resident
+        self.photometric = check_spec(photometric) if photometric is not None else None
         self.B, self.T = int(batch_size), int(seq_len)
         self.factor = crop_factor
         self.shuffle, self.seed, self.drop_last = shuffle, seed, drop_last
@@ -215,6 +220,9 @@ class ResidentBatchLoader:
         if self.shuffle:
             ids = ids[np.random.default_rng((self.seed + self.epoch) * 7919 + self.res.rank).permutation(len(ids))]
         rng = np.random.default_rng((self.seed + 1) * 1_000_003 + self.epoch * 7919 + self.res.rank)
+        # the photometric draws have a generator of their own: boxes and shuffle are the same with the option off
+        photo_rng = (photometric_generator(self.seed, self.epoch, self.res.rank)
+                     if self.photometric is not None else None)
         h0, w0 = self.res.shard.frame_shape[:2]
         st = self.stats = {"batches": 0, "fill_s": 0.0, "gather_s": 0.0, "wait_s": 0.0}
         for i in range(len(self)):
@@ -227,14 +235,19 @@ class ResidentBatchLoader:
             boxes = torch.empty((b, self.T, 4), dtype=torch.int32, pin_memory=self.pin)
             rows.numpy()[:] = self.res.local_rows(widx, self.T)
             boxes.numpy()[:] = crop_boxes(rng, b * self.T, h0, w0, self.factor).reshape(b, self.T, 4)
+            plan = {"plan_rows": rows, "crop_boxes": boxes}
+            if photo_rng is not None:
+                plan["photometric"] = torch.empty((b, 4), dtype=torch.float32, pin_memory=self.pin)
+                plan["photometric"].numpy()[:] = photometric_params(photo_rng, b, self.photometric)
             st["fill_s"] += time.perf_counter() - t0
             st["batches"] += 1
-            yield {"plan_rows": rows, "crop_boxes": boxes}
+            yield plan
 
 
 def decode_resident(res: ResidentShard, batch: Dict, H: int, W: int) -> Dict:
     """Plan -> the model's batch (``image`` [B, T, 3, H, W] uint8, embeddings, action labels) from the resident
-    tables; other batches pass through unchanged."""
+    tables; a ``photometric`` entry [B, 4] is applied to the decoded image in place.  Other batches pass through
+    unchanged."""
     if "plan_rows" not in batch:
         return batch
     rows, boxes = batch["plan_rows"], batch["crop_boxes"]
@@ -249,5 +262,5 @@ def decode_resident(res: ResidentShard, batch: Dict, H: int, W: int) -> Dict:
         img = img.to(res.device)
     return {"action_label": {"terminate_episode": res.is_terminal.index_select(0, flat).view(B, T),
                              "action": res.action.index_select(0, flat).view(B, T, 2)},
-            "train_observation": {"image": img.view(B, T, 3, H, W),
+            "train_observation": {"image": apply_to_decoded(img.view(B, T, 3, H, W), batch.get("photometric")),
                                   "natural_language_embedding": res.instruction.index_select(0, flat).view(B, T, -1)}}

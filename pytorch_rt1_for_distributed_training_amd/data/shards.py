@@ -30,6 +30,8 @@ from typing import Dict, Iterator, List, Optional, Sequence
 import numpy as np
 import torch
 
+from .photometric import apply_to_decoded, check_spec, photometric_generator, photometric_params
+
 FRAMES = "frames.u8"
 META = "meta.npz"
 
@@ -114,8 +116,13 @@ class ShardBatchLoader:
 
     def __init__(self, path: str, batch_size: int, seq_len: int, crop_factor: Optional[float] = 0.95,
                  shuffle: bool = True, rank: int = 0, world: int = 1, seed: int = 0, drop_last: bool = True,
-                 threads: int = 8, pin: Optional[bool] = None, prefetch: int = 2, reuse_buffers: int = 0):
+                 threads: int = 8, pin: Optional[bool] = None, prefetch: int = 2, reuse_buffers: int = 0,
+                 photometric=None):
+        """``photometric``: a ``data.augment.PhotometricDistortions`` range spec; every batch then carries one
+        ``photometric`` row (db, fs, dh, fc) per window for :func:`decode_on_device` (data/photometric.py).  Training
+        loaders only."""
         self.shard = Shard(path)
+        self.photometric = check_spec(photometric) if photometric is not None else None
         self.B, self.T = int(batch_size), int(seq_len)
         self.factor = crop_factor
         self.shuffle, self.rank, self.world, self.seed = shuffle, rank, world, seed
@@ -166,11 +173,15 @@ class ShardBatchLoader:
     def _new(self, b: int) -> Dict[str, torch.Tensor]:
         h, w, c = self.shard.frame_shape
         mk = lambda shape, dt: torch.empty(shape, dtype=dt, pin_memory=self.pin)
-        return {"raw": mk((b, self.T, h, w, c), torch.uint8), "boxes": mk((b, self.T, 4), torch.int32),
-                "emb": mk((b, self.T, 512), torch.float32), "act": mk((b, self.T, 2), torch.float32),
-                "term": mk((b, self.T), torch.long)}
+        buf = {"raw": mk((b, self.T, h, w, c), torch.uint8), "boxes": mk((b, self.T, 4), torch.int32),
+               "emb": mk((b, self.T, 512), torch.float32), "act": mk((b, self.T, 2), torch.float32),
+               "term": mk((b, self.T), torch.long)}
+        if self.photometric is not None:
+            buf["photometric"] = mk((b, 4), torch.float32)
+        return buf
 
-    def _fill(self, pool, widx: np.ndarray, rng: np.random.Generator) -> Dict:
+    def _fill(self, pool, widx: np.ndarray, rng: np.random.Generator,
+              photo_rng: Optional[np.random.Generator] = None) -> Dict:
         b = len(widx)
         buf = self._alloc(b)
         rows = self.shard.frame_index(widx, self.T)                       # [b, T]
@@ -198,14 +209,18 @@ class ShardBatchLoader:
         for f in futs:
             f.result()
         self.stats["gather_s"] += time.perf_counter() - tg
-        return {"action_label": {"terminate_episode": buf["term"], "action": buf["act"]},
-                "train_observation": {"raw_frames": buf["raw"], "crop_boxes": buf["boxes"],
-                                      "natural_language_embedding": buf["emb"]}}
+        obs = {"raw_frames": buf["raw"], "crop_boxes": buf["boxes"], "natural_language_embedding": buf["emb"]}
+        if self.photometric is not None:
+            buf["photometric"].numpy()[:] = photometric_params(photo_rng, b, self.photometric)
+            obs["photometric"] = buf["photometric"]
+        return {"action_label": {"terminate_episode": buf["term"], "action": buf["act"]}, "train_observation": obs}
 
     def __iter__(self) -> Iterator[Dict]:
         idx = self._indices()
         nb = len(self)
         rng = np.random.default_rng((self.seed + 1) * 1_000_003 + self.epoch * 7919 + self.rank)
+        # the photometric draws have a generator of their own: boxes and shuffle are the same with the option off
+        photo_rng = photometric_generator(self.seed, self.epoch, self.rank) if self.photometric is not None else None
         q: "queue.Queue" = queue.Queue(maxsize=self.prefetch)
         stop = threading.Event()
         st = self.stats = {"batches": 0, "fill_s": 0.0, "gather_s": 0.0, "wait_s": 0.0}
@@ -217,7 +232,7 @@ class ShardBatchLoader:
                         if stop.is_set():
                             return
                         t0 = time.perf_counter()
-                        item = self._fill(pool, idx[i * self.B:(i + 1) * self.B], rng)
+                        item = self._fill(pool, idx[i * self.B:(i + 1) * self.B], rng, photo_rng)
                         st["fill_s"] += time.perf_counter() - t0
                         st["batches"] += 1
                         q.put(item)
@@ -271,7 +286,8 @@ def gpu_crop_supported(h0: int, w0: int, H: int, W: int) -> bool:
 
 def decode_on_device(batch: Dict, H: int, W: int) -> Dict:
     """Replace ``raw_frames`` + ``crop_boxes`` by the cropped, resized ``image`` [B, T, 3, H, W] uint8 (on the
-    batch's device: the HIP kernel on GPU, Pillow on CPU).  Other batches pass through unchanged."""
+    batch's device: the HIP kernel on GPU, Pillow on CPU).  A ``photometric`` entry [B, 4] (the loader's option) is
+    applied to the decoded image in place and dropped.  Other batches pass through unchanged."""
     obs = batch.get("train_observation", {})
     if "raw_frames" not in obs:
         return batch
@@ -283,8 +299,8 @@ def decode_on_device(batch: Dict, H: int, W: int) -> Dict:
     else:
         # CPU batches, and downscales past the GPU kernel's tap budget (> ~7x): Pillow, exact by construction
         img = _pil_crop_resize(raw, boxes, H, W).to(raw.device)
-    obs2 = {k: v for k, v in obs.items() if k not in ("raw_frames", "crop_boxes")}
-    obs2["image"] = img.view(B, T, 3, H, W)
+    obs2 = {k: v for k, v in obs.items() if k not in ("raw_frames", "crop_boxes", "photometric")}
+    obs2["image"] = apply_to_decoded(img.view(B, T, 3, H, W), obs.get("photometric"))
     out = dict(batch)
     out["train_observation"] = obs2
     return out
