@@ -90,6 +90,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--backend", choices=["auto", "hip", "torch"], default="auto")
     p.add_argument("--num_layers", type=int, default=8)
     p.add_argument("--weight_decay", type=float, default=0.0, help="AdamW decoupled decay (0 = Adam, reference)")
+    p.add_argument("--optimizer", choices=["adam", "lamb"], default="adam",
+                   help="lamb: layer-wise trust ratios (LAMB) on Adam's moments -- every tensor's update is scaled to "
+                        "lr * ||p|| / ||update||, for large effective batches; the --no_decay_norm_bias groups keep "
+                        "the plain step; checkpoints are interchangeable with adam's")
     p.add_argument("--no_decay_norm_bias", action="store_true",
                    help="--weight_decay skips BatchNorm / LayerNorm scales and shifts, every bias and the embeddings "
                         "(their own parameter group inside the one fused Adam launch)")
@@ -313,8 +317,12 @@ def train(args):
                          ema_warmup=not args.no_ema_warmup, no_decay_norm_bias=args.no_decay_norm_bias,
                          backbone_lr_mult=args.backbone_lr_mult, pretrained=bool(args.pretrained or args.resume),
                          lr_schedule=lr_schedule, label_smoothing=args.label_smoothing, z_loss=args.z_loss,
-                         token_accuracy=args.token_accuracy)
+                         token_accuracy=args.token_accuracy, optimizer=args.optimizer)
     if ctx.is_main:
+        if args.optimizer != "adam":
+            off = [n for n in engine.optimizer.group_names if n.endswith("no_decay")]
+            print(f"[train] optimizer {args.optimizer}: layer-wise trust ratios on {len(engine.flat.params)} tensors"
+                  + (f", not on the groups {off}" if off else ""), flush=True)
         print(f"[train] gradient_clip_val {args.gradient_clip_val if args.gradient_clip_val > 0 else 'off'}, "
               f"skip_nonfinite_steps {'on' if args.skip_nonfinite_steps else 'off'}, "
               f"accumulate_grad_batches {args.accumulate_grad_batches}", flush=True)

@@ -206,6 +206,185 @@ void flat_adam_dev(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v, at::T
                  W);
 }
 
+// The tensor tables of the LAMB step (csrc/kernels/lamb.hip) from the host's description of the flat layout, checked
+// here once so that the per-step binding never has to read a device table back: tensor_chunk_start int32[nT + 1] (CPU),
+// the 64-float chunks [start[i], start[i + 1]) of tensor i, and tensor_adapt uint8[nT] (CPU).  Returns their device
+// copies and chunk_tensor uint16[n / 64], the tensor of every chunk.
+std::vector<at::Tensor> lamb_tables(at::Tensor tensor_chunk_start, at::Tensor tensor_adapt, int64_t n,
+                                    at::Device device) {
+    const char* W = "lamb_tables";
+    TORCH_CHECK(tensor_chunk_start.device().is_cpu() && tensor_chunk_start.scalar_type() == at::kInt &&
+                tensor_chunk_start.dim() == 1 && tensor_chunk_start.is_contiguous(), W,
+                ": tensor_chunk_start must be a contiguous CPU int32 vector");
+    TORCH_CHECK(tensor_adapt.device().is_cpu() && tensor_adapt.scalar_type() == at::kByte && tensor_adapt.dim() == 1 &&
+                tensor_adapt.is_contiguous(), W, ": tensor_adapt must be a contiguous CPU uint8 vector");
+    TORCH_CHECK(n > 0 && n % 64 == 0 && n / 64 <= INT32_MAX, W, ": n is ", n, ", not a positive multiple of 64 (below "
+                "2^37)");
+    const int64_t nT = tensor_chunk_start.numel() - 1, C = n / 64;
+    TORCH_CHECK(nT >= 1, W, ": tensor_chunk_start has ", nT + 1, " entries, expected one more than the tensors (>= 2)");
+    TORCH_CHECK(nT <= 65535, W, ": tensor_chunk_start describes ", nT, " tensors, chunk_tensor (uint16) holds at most "
+                "65535");
+    TORCH_CHECK(tensor_adapt.numel() == nT, W, ": tensor_adapt has ", tensor_adapt.numel(), " entries, expected ", nT,
+                " (one per tensor)");
+    const int32_t* s = tensor_chunk_start.data_ptr<int32_t>();
+    TORCH_CHECK(s[0] == 0, W, ": tensor_chunk_start starts at ", s[0], ", expected 0");
+    for (int64_t i = 0; i < nT; ++i)
+        TORCH_CHECK(s[i + 1] >= s[i], W, ": tensor_chunk_start decreases at entry ", i + 1, " (", s[i], " -> ",
+                    s[i + 1], ")");
+    TORCH_CHECK(s[nT] == C, W, ": tensor_chunk_start ends at ", s[nT], ", expected n / 64 = ", C);
+    at::Tensor table = at::empty({C}, at::TensorOptions().dtype(at::kUInt16));
+    uint16_t* t = table.data_ptr<uint16_t>();
+    for (int64_t i = 0; i < nT; ++i) std::fill(t + s[i], t + s[i + 1], (uint16_t)i);
+    return {tensor_chunk_start.to(device), tensor_adapt.to(device), table.to(device)};
+}
+
+// The LAMB step with {step, lr} on the device, in every form of flat_adam_dev (same optional tensors, same meaning):
+// lamb_moments, lamb_trust, lamb_apply on the current stream (csrc/kernels/lamb.hip).  chunk_sums fp32[n / 64, 2] is
+// the workspace between them; trust fp32[nT] and norms fp32[nT, 2] receive the trust ratios and {||p||, ||u||}.
+// tensor_chunk_start int32[nT + 1], tensor_adapt uint8[nT] and chunk_tensor uint16[n / 64] are lamb_tables' (their
+// contents are checked there; the kernels clamp every entry they index with).  only: 0 = the three launches, the
+// optimizer step; 1, 2, 3 = that launch alone (lamb_kernel_alone below).
+void lamb_launches(const char* W, at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v, at::Tensor state,
+                   const OptT& ema, const OptT& ema_state, const OptT& clip_state, const OptT& group_state,
+                   const OptT& chunk_group, at::Tensor tensor_chunk_start, at::Tensor tensor_adapt,
+                   at::Tensor chunk_tensor, at::Tensor chunk_sums, at::Tensor trust, at::Tensor norms, double beta1,
+                   double beta2, double eps, double weight_decay, double grad_scale, double one_minus_decay,
+                   bool warmup, int only) {
+    const int64_t n = check_adam_buffers(p, g, m, v, W);
+    TORCH_CHECK(n > 0 && n % 64 == 0 && n / 64 <= INT32_MAX, W, ": param has ", n,
+                " elements, not a positive multiple of 64");
+    const int64_t C = n / 64;
+    const auto dev = p.device();
+    check_dev(state, "state", at::kFloat);
+    TORCH_CHECK(state.numel() >= 2, W, ": state has ", state.numel(), " entries, expected {step, lr}");
+    TORCH_CHECK(state.device() == dev, W, ": state on another device");
+    check_dev(tensor_chunk_start, "tensor_chunk_start", at::kInt);
+    check_dev(tensor_adapt, "tensor_adapt", at::kByte);
+    check_dev(chunk_sums, "chunk_sums", at::kFloat);
+    check_dev(trust, "trust", at::kFloat);
+    check_dev(norms, "norms", at::kFloat);
+    const int64_t nT = tensor_chunk_start.numel() - 1;
+    TORCH_CHECK(nT >= 1, W, ": tensor_chunk_start has ", nT + 1, " entries, expected one more than the tensors (>= 2)");
+    TORCH_CHECK(nT <= 65535, W, ": tensor_chunk_start describes ", nT, " tensors, chunk_tensor (uint16) holds at most "
+                "65535");
+    TORCH_CHECK(tensor_adapt.numel() == nT, W, ": tensor_adapt has ", tensor_adapt.numel(), " entries, expected ", nT,
+                " (one per tensor of tensor_chunk_start)");
+    TORCH_CHECK(chunk_sums.numel() == 2 * C, W, ": chunk_sums has ", chunk_sums.numel(), " entries, expected ", 2 * C,
+                " (two per 64 elements)");
+    TORCH_CHECK(trust.numel() == nT, W, ": trust has ", trust.numel(), " entries, expected ", nT, " (one per tensor)");
+    TORCH_CHECK(norms.numel() == 2 * nT, W, ": norms has ", norms.numel(), " entries, expected ", 2 * nT,
+                " (two per tensor)");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(chunk_sums.data_ptr()) % 8 == 0 &&
+                reinterpret_cast<uintptr_t>(norms.data_ptr()) % 8 == 0, W,
+                ": chunk_sums and norms must be 8-byte aligned");
+    TORCH_CHECK(tensor_chunk_start.device() == dev && tensor_adapt.device() == dev && chunk_sums.device() == dev &&
+                trust.device() == dev && norms.device() == dev, W, ": tensors on different devices");
+    check_dev(chunk_tensor, "chunk_tensor", at::kUInt16);
+    TORCH_CHECK(chunk_tensor.numel() == C, W, ": chunk_tensor has ", chunk_tensor.numel(), " entries, expected ", C,
+                " (one per 64 elements)");
+    TORCH_CHECK(chunk_tensor.device() == dev, W, ": chunk_tensor on another device");
+    const uint16_t* ct = chunk_tensor.data_ptr<uint16_t>();
+    const float* cs = nullptr;
+    if (given(clip_state)) {
+        check_clip_state(*clip_state, W);
+        TORCH_CHECK(clip_state->device() == dev, W, ": clip_state on another device");
+        cs = clip_state->data_ptr<float>();
+    }
+    const bool groups = given(group_state);
+    TORCH_CHECK(groups == given(chunk_group), W, ": group_state and chunk_group go together (both or neither)");
+    const float* gst = nullptr;
+    const uint8_t* tab = nullptr;
+    int64_t G = 0;
+    if (groups) {
+        check_dev(*group_state, "group_state", at::kFloat);
+        check_dev(*chunk_group, "chunk_group", at::kByte);
+        TORCH_CHECK(chunk_group->numel() == C, W, ": chunk_group has ", chunk_group->numel(), " entries, expected ", C,
+                    " (one per 64 elements)");
+        G = group_state->numel() / 4;
+        TORCH_CHECK(group_state->numel() % 4 == 0 && G >= 1 && G <= 16, W, ": group_state has ", group_state->numel(),
+                    " entries, expected 4 per group for 1 to 16 groups");
+        TORCH_CHECK(aligned16(*group_state), W, ": group_state must be 16-byte aligned");
+        TORCH_CHECK(group_state->device() == dev && chunk_group->device() == dev, W,
+                    ": group_state / chunk_group on another device");
+        gst = group_state->data_ptr<float>();
+        tab = chunk_group->data_ptr<uint8_t>();
+    }
+    float* e = nullptr;
+    float* es = nullptr;
+    TORCH_CHECK(given(ema) == given(ema_state), W, ": ema and ema_state go together (both or neither)");
+    if (given(ema)) {
+        check_dev(*ema, "ema", at::kFloat);
+        check_dev(*ema_state, "ema_state", at::kFloat);
+        TORCH_CHECK(ema->numel() == n, W, ": ema has ", ema->numel(), " elements, param ", n);
+        TORCH_CHECK(ema_state->numel() >= 4 && aligned16(*ema_state), W, ": ema_state must be fp32[4], 16-byte aligned");
+        TORCH_CHECK(aligned16(*ema), W, ": ema must be 16-byte aligned");
+        TORCH_CHECK(ema->device() == dev && ema_state->device() == dev, W, ": ema / ema_state on another device");
+        TORCH_CHECK(one_minus_decay > 0.0 && one_minus_decay <= 1.0, W, ": one_minus_decay must be in (0, 1]");
+        e = ema->data_ptr<float>();
+        es = ema_state->data_ptr<float>();
+    }
+    // what the kernels write (m, v, p, ema, ema_state, chunk_sums, trust, norms) aliases nothing else they touch
+    std::vector<const at::Tensor*> written = {&p, &m, &v, &chunk_sums, &trust, &norms};
+    std::vector<const at::Tensor*> all = {&p, &g, &m, &v, &state, &tensor_chunk_start, &tensor_adapt, &chunk_tensor,
+                                          &chunk_sums, &trust, &norms};
+    if (e != nullptr) {
+        written.push_back(&*ema);
+        written.push_back(&*ema_state);
+        all.push_back(&*ema);
+        all.push_back(&*ema_state);
+    }
+    if (cs != nullptr) all.push_back(&*clip_state);
+    if (groups) {
+        all.push_back(&*group_state);
+        all.push_back(&*chunk_group);
+    }
+    for (const at::Tensor* w : written)
+        for (const at::Tensor* o : all)
+            TORCH_CHECK(w == o || !overlaps(*w, *o), W, ": a buffer the kernels write aliases another argument");
+    if (only == 0 || only == 1)
+        check_launch(rt1_lamb_moments(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(),
+                                      v.data_ptr<float>(), n, state.data_ptr<float>(), cs, gst, tab, (int)G,
+                                      (float)beta1, (float)beta2, (float)eps, (float)weight_decay, (float)grad_scale,
+                                      chunk_sums.data_ptr<float>(), cur_stream()),
+                     "lamb_moments");
+    if (only == 0 || only == 2)
+        check_launch(rt1_lamb_trust(chunk_sums.data_ptr<float>(), n, tensor_chunk_start.data_ptr<int32_t>(),
+                                    tensor_adapt.data_ptr<uint8_t>(), (int)nT, cs, trust.data_ptr<float>(),
+                                    norms.data_ptr<float>(), cur_stream()),
+                     "lamb_trust");
+    if (only == 0 || only == 3)
+        check_launch(rt1_lamb_apply(p.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), n,
+                                    state.data_ptr<float>(), cs, e, es, gst, tab, (int)G, trust.data_ptr<float>(), ct,
+                                    (int)nT, (float)beta1, (float)beta2, (float)eps, (float)weight_decay,
+                                    (float)one_minus_decay, warmup ? 1 : 0, cur_stream()),
+                     "lamb_apply");
+}
+
+void flat_lamb_dev(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v, at::Tensor state, const OptT& ema,
+                   const OptT& ema_state, const OptT& clip_state, const OptT& group_state, const OptT& chunk_group,
+                   at::Tensor tensor_chunk_start, at::Tensor tensor_adapt, at::Tensor chunk_tensor,
+                   at::Tensor chunk_sums, at::Tensor trust, at::Tensor norms, double beta1, double beta2, double eps,
+                   double weight_decay, double grad_scale, double one_minus_decay, bool warmup) {
+    lamb_launches("flat_lamb_dev", p, g, m, v, state, ema, ema_state, clip_state, group_state, chunk_group,
+                  tensor_chunk_start, tensor_adapt, chunk_tensor, chunk_sums, trust, norms, beta1, beta2, eps,
+                  weight_decay, grad_scale, one_minus_decay, warmup, 0);
+}
+
+// For tools/bench_lamb.py only: ONE of the three launches of flat_lamb_dev (kernel 1 moments, 2 trust, 3 apply) on the
+// same checked arguments, so that each kernel can be timed.  Not an optimizer step: kernel 3 alone applies whatever
+// trust holds.
+void lamb_kernel_alone(int64_t kernel, at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v, at::Tensor state,
+                       const OptT& ema, const OptT& ema_state, const OptT& clip_state, const OptT& group_state,
+                       const OptT& chunk_group, at::Tensor tensor_chunk_start, at::Tensor tensor_adapt,
+                       at::Tensor chunk_tensor, at::Tensor chunk_sums, at::Tensor trust, at::Tensor norms,
+                       double beta1, double beta2, double eps, double weight_decay, double grad_scale,
+                       double one_minus_decay, bool warmup) {
+    TORCH_CHECK(kernel >= 1 && kernel <= 3, "lamb_kernel_alone: kernel is ", kernel, ", expected 1, 2 or 3");
+    lamb_launches("lamb_kernel_alone", p, g, m, v, state, ema, ema_state, clip_state, group_state, chunk_group,
+                  tensor_chunk_start, tensor_adapt, chunk_tensor, chunk_sums, trust, norms, beta1, beta2, eps,
+                  weight_decay, grad_scale, one_minus_decay, warmup, (int)kernel);
+}
+
 // per-step learning-rate schedule formed on the device (lr_schedule_kernel): state[1] and, when given, group_state[g][0]
 // <- lr_base[g] * f(t); sched_state fp32[4] <- {f, t, 0, 0}.  kind 0..3 = constant, linear, cosine, rsqrt.
 void lr_schedule_dev(at::Tensor state, at::Tensor lr_base, at::Tensor sched_state, const OptT& group_state,
@@ -1603,6 +1782,11 @@ PYBIND11_MODULE(_rt1_hip, m) {
     m.def("flat_adam_dev", &flat_adam_dev,
           "fused Adam/AdamW, step/lr read from a device tensor (graph-replayable); optionally obeying clip_state, "
           "updating the EMA of the weights, with lr / weight_decay per parameter group");
+    m.def("lamb_tables", &lamb_tables,
+          "checked device tables of the LAMB step: (tensor_chunk_start, tensor_adapt, chunk_tensor uint16 per chunk)");
+    m.def("flat_lamb_dev", &flat_lamb_dev,
+          "LAMB (layer-wise trust ratios) over flat fp32 buffers in three launches, every form of flat_adam_dev");
+    m.def("lamb_kernel_alone", &lamb_kernel_alone, "one of flat_lamb_dev's three launches, for timing (not a step)");
     m.def("lr_schedule_dev", &lr_schedule_dev,
           "per-step lr schedule on the device: state[1] / group_state[g][0] <- lr_base[g] * f(effective Adam step)");
     m.def("gradnorm_partials", &gradnorm_partials, "fp64 partial sums grad_sumsq writes for n floats");

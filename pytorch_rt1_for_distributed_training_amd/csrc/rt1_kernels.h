@@ -33,6 +33,28 @@ int rt1_lr_schedule_dev(float* state, const float* clip_state, const float* lr_b
                         float* sched_state, int G, int kind, int64_t warmup, int64_t decay, double min_ratio,
                         hipStream_t stream);
 
+// lamb.hip: layer-wise trust ratios (LAMB) over the same flat buffers, three launches in this order, every form of
+// rt1_flat_adam_dev (clip_state, ema, groups: null when absent).  n is a positive multiple of 64 and C = n / 64;
+// tensor_chunk_start int32[nT + 1] gives the chunks [start[i], start[i + 1]) of tensor i (a value outside [0, C] is
+// read as the nearer bound), tensor_adapt uint8[nT] is 0 for a tensor whose trust ratio stays 1.
+//   moments  m, v <- Adam's, and chunk_sums fp32[C, 2] <- {sum p^2, sum u^2} of each 64-float chunk, u the update
+//            direction (m / bc1) / (sqrt(v) / sqrt(bc2) + eps) + wd * p; g and p are only read;
+//   trust    trust fp32[nT] <- ||p_i|| / ||u_i|| (1 when either is 0 or the tensor is not adapted) and norms
+//            fp32[nT, 2] <- {||p_i||, ||u_i||}, from the chunk sums in index order in fp64;
+//   apply    p <- p - (lr * trust) * u with the same u, ema as in adam.hip; chunk_tensor uint16[C] names the tensor of
+//            each chunk (an entry >= nT is read as nT - 1).
+// A skipped step (clip_state[2] == 0) writes nothing in any of the three.
+int rt1_lamb_moments(const float* p, const float* g, float* m, float* v, int64_t n, const float* state,
+                     const float* clip_state, const float* group_state, const uint8_t* chunk_group, int G,
+                     float beta1, float beta2, float eps, float weight_decay, float grad_scale, float* chunk_sums,
+                     hipStream_t stream);
+int rt1_lamb_trust(const float* chunk_sums, int64_t n, const int32_t* tensor_chunk_start, const uint8_t* tensor_adapt,
+                   int nT, const float* clip_state, float* trust, float* norms, hipStream_t stream);
+int rt1_lamb_apply(float* p, const float* m, const float* v, int64_t n, const float* state, const float* clip_state,
+                   float* ema, float* ema_state, const float* group_state, const uint8_t* chunk_group, int G,
+                   const float* trust, const uint16_t* chunk_tensor, int nT, float beta1, float beta2, float eps,
+                   float weight_decay, float one_minus_decay, int warmup, hipStream_t stream);
+
 // gradnorm.hip (deterministic global gradient norm -> clip_state fp32[8] = {norm, coef, ok, skipped steps, clipped
 // steps, consecutive skipped steps, 0, 0}; rt1_gradnorm_partials: workgroups / fp64 partials for n floats, a function
 // of n alone, 0 for n <= 0)

@@ -32,6 +32,13 @@ per step comes from the host: one tiny launch in front of the Adam launch (``ops
 factor on the device from the effective Adam step ``t`` -- the ``t`` of the bias corrections and of the EMA warm-up,
 which does not count skipped steps -- and writes ``base_g * f`` where the Adam kernels read their lr.  ``param_groups``
 keep the base learning rates, so ``MultiStepLR`` composes with it.
+
+Layer-wise trust ratios (``layer_adapt=True``, off by default; LAMB, You et al. 2020): every tensor's Adam direction
+``u = m_hat / (sqrt(v_hat) + eps) + wd * p`` is applied with the step ``lr * ||p|| / ||u||`` (the ratio is 1 when either
+norm is 0 and for the tensors of a group that says ``layer_adapt: False`` -- ``build_param_groups`` says so for the
+no-decay groups).  Three launches take the place of the Adam launch (``ops.adam.flat_lamb_dev_step``); clipping, the
+schedule, the EMA and the groups work as before, and ``m, v`` and the step are Adam's, so checkpoints are
+interchangeable.
 """
 from __future__ import annotations
 
@@ -109,16 +116,20 @@ class FlatAdam(torch.optim.Optimizer):
                  use_kernel: Optional[bool] = None, max_grad_norm: Optional[float] = None,
                  skip_nonfinite: bool = False, ema_decay: float = 0.0, ema_warmup: bool = True,
                  param_names: Optional[Dict[int, str]] = None, groups: Optional[Sequence[dict]] = None,
-                 lr_schedule: Optional[dict] = None):
+                 lr_schedule: Optional[dict] = None, layer_adapt: bool = False):
         lr_schedule = checked_lr_schedule(lr_schedule)
         if not 0.0 <= float(ema_decay) < 1.0:
             raise ValueError(f"ema_decay must be in [0, 1) (0 = off), got {ema_decay!r}")
         self.flat = flat
         params = list(all_params) if all_params is not None else list(flat.params)
         decoupled = weight_decay > 0
+        group_adapt = None
         if groups is not None:
             params = self._checked_groups(groups, params)
             decoupled = any(g.get("weight_decay", weight_decay) > 0 for g in params)
+            # a group's layer_adapt flag is a property of the run, not of the checkpoint: it is kept here and the
+            # param_groups (and with them state_dict()) hold the keys they always held
+            group_adapt = [bool(g.pop("layer_adapt", True)) for g in params]
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False,
                                       maximize=False, foreach=None, capturable=False, differentiable=False,
                                       fused=None, decoupled_weight_decay=decoupled))
@@ -184,6 +195,41 @@ class FlatAdam(torch.optim.Optimizer):
         if lr_schedule is not None:
             self.lr_base = torch.zeros(len(self.param_groups), dtype=torch.float32, device=flat.data.device)
             self.sched_state = torch.zeros(4, dtype=torch.float32, device=flat.data.device)
+        # layer-wise trust ratios (LAMB; off by default: no tensor, no launch).  Tensor i of flat.params is the chunks
+        # tensor_chunk_start[i] .. tensor_chunk_start[i + 1] of the flat buffer (its padding included);
+        # tensor_adapt[i] = 0 keeps its trust ratio at 1 (the parameters of a group with layer_adapt: False).  The
+        # step is then ops.adam.flat_lamb_dev_step -- three launches in the place of the Adam launch -- which leaves
+        # trust fp32[nT] and norms fp32[nT, 2] = {||p||, ||u||} of the last applied update.  m, v and the step are
+        # Adam's, so the state dict is too
+        self.layer_adapt = bool(layer_adapt)
+        self.kind = "lamb" if self.layer_adapt else "adam"
+        self.tensor_chunk_start = self.tensor_adapt = self.chunk_tensor = None
+        self.chunk_sums = self.trust = self.norms = None
+        if self.layer_adapt:
+            starts, adapt = self.layer_tables(flat, self.param_groups, group_adapt)
+            dev = flat.data.device
+            nT = len(adapt)
+            if self._kernel is not None:
+                self.tensor_chunk_start, self.tensor_adapt, self.chunk_tensor = self._kernel.lamb_tables(
+                    starts, adapt, flat.numel, dev)
+                self.chunk_sums = torch.zeros(flat.numel // ALIGN, 2, dtype=torch.float32, device=dev)
+            else:
+                self.tensor_chunk_start = torch.tensor(starts, dtype=torch.int32, device=dev)
+                self.tensor_adapt = torch.tensor(adapt, dtype=torch.uint8, device=dev)
+            self.trust = torch.ones(nT, dtype=torch.float32, device=dev)
+            self.norms = torch.zeros(nT, 2, dtype=torch.float32, device=dev)
+
+    @staticmethod
+    def layer_tables(flat: FlatParameters, param_groups: Sequence[dict],
+                     group_adapt: Optional[Sequence[bool]] = None) -> Tuple[List[int], List[int]]:
+        """``(tensor_chunk_start [nT + 1], tensor_adapt [nT])`` of ``flat.params`` from ``flat.offsets``: a tensor owns
+        the 64-float chunks from its offset to the next tensor's (its zero padding included), and is adapted unless its
+        group says ``layer_adapt: False`` (``group_adapt[gi]``, default: every group adapts)."""
+        starts = [o // ALIGN for o in flat.offsets] + [flat.numel // ALIGN]
+        if group_adapt is None:
+            return starts, [1] * len(flat.params)
+        adapt_of = {id(p): int(group_adapt[gi]) for gi, g in enumerate(param_groups) for p in g["params"]}
+        return starts, [adapt_of[id(p)] for p in flat.params]
 
     @torch.no_grad()
     def step(self, closure=None, grad_scale: float = 1.0):
@@ -214,6 +260,18 @@ class FlatAdam(torch.optim.Optimizer):
                 self._kernel.lr_schedule_dev(self.dev_state, self.lr_base, self.sched_state,
                                              group_state=self.group_state, clip_state=self.clip_state,
                                              **self.lr_schedule)
+            if self.layer_adapt:
+                # the same forms and operands, three launches: moments + chunk sums, per-tensor norms, apply
+                self._kernel.flat_lamb_dev_step(self.flat.data, self.flat.grad, self.exp_avg, self.exp_avg_sq,
+                                                self.dev_state, tensor_chunk_start=self.tensor_chunk_start,
+                                                tensor_adapt=self.tensor_adapt, chunk_tensor=self.chunk_tensor,
+                                                chunk_sums=self.chunk_sums, trust=self.trust, norms=self.norms,
+                                                ema=self.ema, ema_state=self.ema_state, clip_state=self.clip_state,
+                                                group_state=self.group_state if grouped else None,
+                                                chunk_group=self.chunk_group if grouped else None, beta1=b1,
+                                                beta2=b2, eps=eps, weight_decay=wd, grad_scale=grad_scale,
+                                                one_minus_decay=self._omd, warmup=self.ema_warmup)
+                return loss
             # one launch in every form: clip_state and ema are None when off, the groups' tensors go only if grouped
             self._kernel.flat_adam_dev_step(self.flat.data, self.flat.grad, self.exp_avg, self.exp_avg_sq,
                                             self.dev_state, ema=self.ema, ema_state=self.ema_state,
@@ -244,24 +302,66 @@ class FlatAdam(torch.optim.Optimizer):
             lr_e, wd_e = self._per_element()         # the same update with lr and wd expanded per element
             if f is not None:
                 lr_e = lr_e * f
-            p.mul_(1.0 - lr_e * wd_e)
-        elif wd:
-            p.mul_(1.0 - lr * wd)
-        self.exp_avg.lerp_(grad, 1.0 - b1)
-        self.exp_avg_sq.mul_(b2).addcmul_(grad, grad, value=1.0 - b2)
-        bc1 = 1.0 - b1 ** t
-        bc2 = 1.0 - b2 ** t
-        denom = (self.exp_avg_sq.sqrt() / math.sqrt(bc2)).add_(eps)
-        if grouped:
-            p.sub_((lr_e / bc1) * (self.exp_avg / denom))
+        if self.layer_adapt:
+            self._lamb_host(p, grad, lr_e if grouped else lr, wd_e if grouped else wd, b1, b2, eps, t)
         else:
-            p.addcdiv_(self.exp_avg, denom, value=-lr / bc1)
+            if grouped:
+                p.mul_(1.0 - lr_e * wd_e)
+            elif wd:
+                p.mul_(1.0 - lr * wd)
+            self._adam_host(p, grad, lr_e if grouped else lr, b1, b2, eps, t, grouped)
         if self.ema_enabled:
             # the kernel's recurrence in torch: omd_t in fp32 from the same t, ema += omd_t * (p - ema)
             omd_t = self._omd_t(t)
             self.ema_state.copy_(torch.stack([omd_t, torch.tensor(float(t)), torch.zeros(()), torch.zeros(())]))
             self.ema.add_((p - self.ema).mul_(omd_t.to(p.device)))
         return loss
+
+    def _adam_host(self, p, grad, lr, b1, b2, eps, t, grouped):
+        """CPU / no-kernel path: moments and the Adam update (``lr`` per element when ``grouped``)."""
+        self.exp_avg.lerp_(grad, 1.0 - b1)
+        self.exp_avg_sq.mul_(b2).addcmul_(grad, grad, value=1.0 - b2)
+        bc1 = 1.0 - b1 ** t
+        bc2 = 1.0 - b2 ** t
+        denom = (self.exp_avg_sq.sqrt() / math.sqrt(bc2)).add_(eps)
+        if grouped:
+            p.sub_((lr / bc1) * (self.exp_avg / denom))
+        else:
+            p.addcdiv_(self.exp_avg, denom, value=-lr / bc1)
+
+    def _lamb_host(self, p, grad, lr, wd, b1, b2, eps, t):
+        """CPU / no-kernel path of the LAMB step: the kernels' update in torch, fp32 with fp64 norms (``lr`` and ``wd``
+        scalars, or per element with several groups)."""
+        self.exp_avg.mul_(b1).add_(grad, alpha=1.0 - b1)
+        self.exp_avg_sq.mul_(b2).addcmul_(grad, grad, value=1.0 - b2)
+        bc1 = 1.0 - b1 ** t
+        bc2 = 1.0 - b2 ** t
+        u = (self.exp_avg / bc1) / (self.exp_avg_sq.sqrt() / math.sqrt(bc2)).add_(eps) + wd * p
+        starts = [int(c) * ALIGN for c in self.tensor_chunk_start.tolist()]
+        adapt = self.tensor_adapt.tolist()
+        pn = torch.stack([p[a:b].double().pow(2).sum().sqrt() for a, b in zip(starts[:-1], starts[1:])])
+        un = torch.stack([u[a:b].double().pow(2).sum().sqrt() for a, b in zip(starts[:-1], starts[1:])])
+        on = torch.tensor(adapt, dtype=torch.bool, device=p.device) & (pn > 0) & (un > 0)
+        trust = torch.where(on, pn / torch.where(un > 0, un, torch.ones_like(un)), torch.ones_like(pn)).float()
+        self.trust.copy_(trust)
+        self.norms.copy_(torch.stack([pn, un], dim=1).float())
+        sizes = torch.tensor([b - a for a, b in zip(starts[:-1], starts[1:])], device=p.device)
+        p.sub_(lr * trust.repeat_interleave(sizes) * u)
+
+    # -------------------------------------------------------------- layer-wise trust ratios
+    def trust_ratios(self) -> Dict[str, torch.Tensor]:
+        """The trust ratio of every tensor of ``flat.params`` at the last applied update, by name: 0-d device views
+        (no sync).  Ones before the first update."""
+        if self.trust is None:
+            raise RuntimeError("layer-wise adaptation is off (layer_adapt = False)")
+        return {name: self.trust[i] for i, name in enumerate(self._param_names())}
+
+    def last_update_norms(self) -> Dict[str, Tuple[torch.Tensor, torch.Tensor]]:
+        """``(||p||, ||u||)`` of every tensor as the last applied update measured them (the weights before that update
+        and its direction before the trust ratio and the learning rate), by name: 0-d device views (no sync)."""
+        if self.norms is None:
+            raise RuntimeError("layer-wise adaptation is off (layer_adapt = False)")
+        return {name: (self.norms[i, 0], self.norms[i, 1]) for i, name in enumerate(self._param_names())}
 
     def _clip_verdict(self, grad: torch.Tensor):
         """CPU / no-kernel path: norm of the (already averaged) gradient -> clip_state, returns (coef, ok)."""
@@ -395,7 +495,7 @@ class FlatAdam(torch.optim.Optimizer):
             raise ValueError(f"FlatAdam takes 1 to {MAX_GROUPS} parameter groups, got {len(groups)}")
         seen: Dict[int, int] = {}
         for gi, g in enumerate(groups):
-            extra = set(g) - {"params", "name", "lr", "weight_decay"}
+            extra = set(g) - {"params", "name", "lr", "weight_decay", "layer_adapt"}
             if extra:
                 raise ValueError(f"parameter group {gi} has unknown keys {sorted(extra)}")
             for p in g["params"]:
@@ -495,6 +595,8 @@ class FlatAdam(torch.optim.Optimizer):
         out = {"state": state, "param_groups": groups}
         if self.lr_schedule is not None:
             out["lr_schedule"] = dict(self.lr_schedule)      # its position is the effective step above
+        if self.layer_adapt:
+            out["optimizer_kind"] = self.kind                # absent: adam (the layout every earlier checkpoint has)
         return out
 
     def load_state_dict(self, sd: Dict):
@@ -581,6 +683,11 @@ def build_param_groups(model: torch.nn.Module, lr: float, weight_decay: float, n
         if no_decay_norm_bias and (p.ndim <= 1 or id(p) in embeddings):
             name += "_no_decay"
         groups[name]["params"].append(p)
+    # under FlatAdam(layer_adapt=True) the no-decay groups keep the plain Adam step size (trust ratio 1), as in the
+    # LAMB paper's BERT recipe; FlatAdam keeps the flag to itself, so param_groups and checkpoints do not carry it
+    for name, g in groups.items():
+        if name.endswith("no_decay"):
+            g["layer_adapt"] = False
     return [g for g in groups.values() if g["params"]]
 
 

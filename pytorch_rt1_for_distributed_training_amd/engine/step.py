@@ -69,6 +69,10 @@ With ``token_accuracy`` every forward adds {pred == label, rows} per action-toke
 launch, part of the captured step; every micro-batch of an accumulation window counts); ``read_token_counters`` reads
 and zeroes them.
 
+``optimizer="lamb"`` (``"adam"`` = off, and then nothing here changes): ``FlatAdam(layer_adapt=True)``, layer-wise trust
+ratios on Adam's moments -- three launches (``ops.adam.flat_lamb_dev_step``) where the Adam launch was, so every step
+path and every option above carries them unchanged; the no-decay groups of ``no_decay_norm_bias`` are not adapted.
+
 No ``network_state`` is fabricated (the reference samples a random one on the
 CPU and copies it to the GPU every step only to read its shape).
 """
@@ -149,6 +153,9 @@ def _test_capture_failure():
         raise RuntimeError("capture failure forced by RT1_TEST_CAPTURE_FAIL")
 
 
+OPTIMIZERS = ("adam", "lamb")     # lamb: FlatAdam(layer_adapt=True), layer-wise trust ratios on the same state
+
+
 class TrainEngine:
     def __init__(self, model: nn.Module, cfg: RT1Config, lr: float = 5e-4, milestones=(50, 75, 90),
                  gamma: float = 0.1, weight_decay: float = 0.0, bucket_cap_mb: float = 32.0,
@@ -158,8 +165,11 @@ class TrainEngine:
                  accumulate_grad_batches: int = 1, ema_decay: float = 0.0, ema_warmup: bool = True,
                  no_decay_norm_bias: bool = False, backbone_lr_mult: float = 1.0,
                  pretrained: Optional[bool] = None, lr_schedule: Optional[dict] = None,
-                 label_smoothing: float = 0.0, z_loss: float = 0.0, token_accuracy: bool = False):
+                 label_smoothing: float = 0.0, z_loss: float = 0.0, token_accuracy: bool = False,
+                 optimizer: str = "adam"):
         from ..models.policy import checked_objective
+        if optimizer not in OPTIMIZERS:
+            raise ValueError(f"optimizer must be one of {OPTIMIZERS}, got {optimizer!r}")
         label_smoothing, z_loss = checked_objective(label_smoothing, z_loss)
         if not isinstance(backbone_lr_mult, (int, float)) or not backbone_lr_mult > 0:
             raise ValueError(f"backbone_lr_mult must be a number > 0, got {backbone_lr_mult!r}")
@@ -231,7 +241,7 @@ class TrainEngine:
                                   all_params=list(self.model.parameters()), max_grad_norm=max_grad_norm,
                                   skip_nonfinite=skip_nonfinite, ema_decay=ema_decay, ema_warmup=ema_warmup,
                                   param_names={id(p): n for n, p in self.model.named_parameters()}, groups=groups,
-                                  lr_schedule=lr_schedule)
+                                  lr_schedule=lr_schedule, layer_adapt=optimizer == "lamb")
         # skip_nonfinite: the forward of a bad batch has already written the BN running statistics when the norm
         # kernel notices, so they live in one flat buffer (the data-parallel one when there is one) with a shadow copy
         # of the last good state; buffer_guard_ advances or rolls back right after the optimizer step

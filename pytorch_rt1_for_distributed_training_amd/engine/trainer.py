@@ -37,6 +37,10 @@ With the engine's ``lr_schedule`` the ``log_every_n_steps`` log point also logs 
 several groups) as the last applied update used them, read back from the device at the point that already synchronises
 for the loss; the per-epoch ``lr-Adam`` stays the base learning rate that ``MultiStepLR`` scales.
 
+With the engine's ``optimizer="lamb"`` the same log point also logs ``trust/min``, ``trust/median`` and ``trust/max``,
+the layer-wise trust ratios of the last applied update (one small device-to-host copy, never per step); ``resume``
+says in one line when the checkpoint was written by the other optimizer kind (the state is the same).
+
 With the engine's ``label_smoothing`` / ``z_loss`` the logged training loss is the regularised objective, so each log
 point also logs ``train_nll_step``, the plain CE of the same batches; ``eval_loss`` / ``test_loss`` are the plain CE in
 any case (the objective applies in training mode only).  With the engine's ``token_accuracy`` each log point logs
@@ -171,6 +175,11 @@ class Trainer:
                                  f"{opt.group_layout(saved['param_groups'])}, this run has {opt.group_layout()}: "
                                  f"resume with the --no_decay_norm_bias / --backbone_lr_mult of the run that wrote it")
             opt.load_state_dict(saved)
+            # Adam and LAMB keep the same state (m, v, step): either continues from the other's checkpoint
+            was, now = saved.get("optimizer_kind", "adam"), getattr(opt, "kind", "adam")
+            if was != now and self.verbose:
+                print(f"[trainer] {path} was written by the {was} optimizer, this run continues with {now} from its "
+                      f"moments and step {opt.step_count}", flush=True)
         if ck.get("lr_schedulers"):
             self.engine.scheduler.load_state_dict(ck["lr_schedulers"][0])
         self.engine.global_step = int(ck.get("global_step", 0))
@@ -300,6 +309,11 @@ class Trainer:
                         lr_shown = metrics["lr-Adam"] = next(iter(now.values()))
                         if len(now) > 1:
                             metrics.update({f"lr/{name}": v for name, v in now.items()})
+                    if getattr(opt, "trust", None) is not None:
+                        # layer-wise trust ratios of the last applied update: one small D2H at this synchronised point
+                        tr = opt.trust.float().cpu()
+                        metrics.update({"trust/min": float(tr.min()), "trust/median": float(tr.median()),
+                                        "trust/max": float(tr.max())})
                     self._log(metrics)
                     window, wn, wcount, wsteps, nwindow = None, 0, None, 0, None
                     if self.verbose:

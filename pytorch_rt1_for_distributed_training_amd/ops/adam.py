@@ -47,6 +47,73 @@ def flat_adam_dev_step(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: tor
                          weight_decay, grad_scale, float(one_minus_decay), bool(warmup))
 
 
+MAX_LAMB_TENSORS = 65535   # chunk_tensor is uint16
+
+
+def lamb_tables(tensor_chunk_start, tensor_adapt, n: int, device):
+    """The checked device tables of ``flat_lamb_dev_step`` for a flat buffer of ``n`` floats: ``tensor_chunk_start``
+    (``nT + 1`` integers: tensor ``i`` is the 64-float chunks ``start[i] .. start[i + 1]``; it must start at 0, never
+    decrease and end at ``n / 64``) and ``tensor_adapt`` (``nT`` flags, 0 = the trust ratio of that tensor stays 1).
+    Returns ``(tensor_chunk_start int32, tensor_adapt uint8, chunk_tensor uint16[n / 64])`` on ``device``."""
+    tcs = torch.as_tensor(tensor_chunk_start, dtype=torch.int32, device="cpu").contiguous()
+    ta = torch.as_tensor(tensor_adapt, device="cpu").to(torch.uint8).contiguous()
+    return tuple(load().lamb_tables(tcs, ta, int(n), torch.device(device)))
+
+
+def flat_lamb_dev_step(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, state: torch.Tensor, *,
+                       tensor_chunk_start: torch.Tensor, tensor_adapt: torch.Tensor, chunk_tensor: torch.Tensor,
+                       chunk_sums: torch.Tensor, trust: torch.Tensor, norms: torch.Tensor,
+                       ema: torch.Tensor = None, ema_state: torch.Tensor = None, clip_state: torch.Tensor = None,
+                       group_state: torch.Tensor = None, chunk_group: torch.Tensor = None, beta1: float, beta2: float,
+                       eps: float, weight_decay: float = 0.0, grad_scale: float = 1.0, one_minus_decay: float = 1.0,
+                       warmup: bool = True):
+    """LAMB (layer-wise trust ratios, ``csrc/kernels/lamb.hip``) in the forms and with the keywords of
+    ``flat_adam_dev_step``: ``m, v`` are Adam's, and with ``u = (m / bc1) / (sqrt(v) / sqrt(bc2) + eps) + wd * p`` every
+    tensor ``i`` of the flat buffer moves by ``p -= (lr * r_i) * u``, ``r_i = ||p_i|| / ||u_i||`` (1 when either norm
+    is 0 or ``tensor_adapt[i] == 0``).  Three launches (moments and per-chunk sums, per-tensor norms, apply), no host
+    read, no atomics; ``g`` is not modified.
+
+    * ``tensor_chunk_start`` int32[nT + 1], ``tensor_adapt`` uint8[nT], ``chunk_tensor`` uint16[n / 64]: what
+      ``lamb_tables`` returns.
+    * ``chunk_sums`` fp32[n / 64, 2]: workspace, ``{sum p^2, sum u^2}`` per 64-float chunk.
+    * ``trust`` fp32[nT] and ``norms`` fp32[nT, 2] ``= {||p_i||, ||u_i||}`` (of the weights before the update).
+
+    A skipped step (``clip_state[2] == 0``) writes nothing."""
+    load().flat_lamb_dev(p, g, m, v, state, ema, ema_state, clip_state, group_state, chunk_group, tensor_chunk_start,
+                         tensor_adapt, chunk_tensor, chunk_sums, trust, norms, beta1, beta2, eps, weight_decay,
+                         grad_scale, float(one_minus_decay), bool(warmup))
+
+
+def reference_lamb_step(p, g, m, v, tensor_chunk_start, tensor_adapt, *, lr, beta1, beta2, eps, weight_decay, step,
+                        grad_scale=1.0, chunk_group=None):
+    """Plain PyTorch oracle of the LAMB update in the dtype of its operands (fp64 for a referee), tensor by tensor.
+    With ``chunk_group``, ``lr`` and ``weight_decay`` are per-group sequences expanded per element as in
+    ``reference_adam_groups_step``; otherwise scalars.  Modifies ``p, m, v`` in place and returns
+    ``(trust [nT], norms [nT, 2])`` in that dtype."""
+    if chunk_group is not None:
+        idx = chunk_group.to(device=p.device, dtype=torch.long).repeat_interleave(CHUNK)
+        lr = torch.as_tensor(lr, dtype=p.dtype, device=p.device)[idx]
+        wd = torch.as_tensor(weight_decay, dtype=p.dtype, device=p.device)[idx]
+    else:
+        lr = torch.full_like(p, lr)
+        wd = torch.full_like(p, weight_decay)
+    g = g * grad_scale
+    m.mul_(beta1).add_(g, alpha=1 - beta1)
+    v.mul_(beta2).addcmul_(g, g, value=1 - beta2)
+    u = (m / (1 - beta1 ** step)) / (v.sqrt() / math.sqrt(1 - beta2 ** step) + eps) + wd * p
+    starts = [int(x) * CHUNK for x in torch.as_tensor(tensor_chunk_start).tolist()]
+    adapt = [int(x) for x in torch.as_tensor(tensor_adapt).tolist()]
+    trust = torch.ones(len(adapt), dtype=p.dtype, device=p.device)
+    norms = torch.zeros(len(adapt), 2, dtype=p.dtype, device=p.device)
+    for i, (a, b) in enumerate(zip(starts[:-1], starts[1:])):
+        norms[i, 0] = p[a:b].pow(2).sum().sqrt()
+        norms[i, 1] = u[a:b].pow(2).sum().sqrt()
+        if adapt[i] and norms[i, 0] > 0 and norms[i, 1] > 0:
+            trust[i] = norms[i, 0] / norms[i, 1]
+        p[a:b].sub_(lr[a:b] * trust[i] * u[a:b])
+    return trust, norms
+
+
 def gradnorm_partials(n: int) -> int:
     """Number of fp64 partial sums ``grad_norm_clip_`` needs for a gradient of ``n`` floats (a function of n alone)."""
     return int(load().gradnorm_partials(int(n)))
