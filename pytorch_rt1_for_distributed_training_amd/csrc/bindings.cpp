@@ -370,6 +370,87 @@ void flat_lamb_dev(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v, at::T
                   weight_decay, grad_scale, one_minus_decay, warmup, 0);
 }
 
+// LAVA pixel-language cross attention, one query per frame (csrc/kernels/lavaxattn.hip).  The shared checks of the
+// forward and the backward: pixels fp32[N, S, 128], the pixel LayerNorm's weight / bias fp32[128], MultiheadAttention's
+// in_proj_weight fp32[384, 128] and in_proj_bias fp32[384], all contiguous, 16-byte aligned, on one device.
+void check_lava_xattn(const char* W, const at::Tensor& pixels, const at::Tensor& ln_w, const at::Tensor& ln_b,
+                      const at::Tensor& in_w, const at::Tensor& in_b) {
+    check_dev(pixels, "pixels", at::kFloat);
+    check_dev(ln_w, "ln_weight", at::kFloat);
+    check_dev(ln_b, "ln_bias", at::kFloat);
+    check_dev(in_w, "in_proj_weight", at::kFloat);
+    check_dev(in_b, "in_proj_bias", at::kFloat);
+    TORCH_CHECK(pixels.dim() == 3 && pixels.size(0) >= 1 && pixels.size(1) >= 1, W, ": pixels must be [N, S, d]");
+    const int64_t d = pixels.size(2);
+    TORCH_CHECK(in_w.dim() == 2 && in_w.size(1) == d && in_w.size(0) == 3 * d && in_b.numel() == 3 * d &&
+                    ln_w.numel() == d && ln_b.numel() == d, W, ": parameter shapes do not match d = ", d);
+    TORCH_CHECK(rt1_lava_xattn_supported((int)d, 2), W, ": d = ", d, " is not supported (d = 128, 2 heads)");
+    TORCH_CHECK(pixels.size(0) * rt1_lava_xattn_chunks(pixels.size(1)) <= INT32_MAX, W, ": too many row chunks");
+    TORCH_CHECK(aligned16(pixels) && aligned16(ln_w) && aligned16(ln_b) && aligned16(in_w) && aligned16(in_b), W,
+                ": tensors must be 16-byte aligned");
+    for (const at::Tensor* t : {&ln_w, &ln_b, &in_w, &in_b})
+        TORCH_CHECK(t->device() == pixels.device(), W, ": tensors on different devices");
+}
+
+void check_lava_frames(const char* W, const at::Tensor& t, const char* name, const at::Tensor& pixels,
+                       std::initializer_list<int64_t> tail) {
+    check_dev(t, name, at::kFloat);
+    std::vector<int64_t> shape{pixels.size(0)};
+    shape.insert(shape.end(), tail);
+    TORCH_CHECK(t.sizes() == at::IntArrayRef(shape), W, ": ", name, " has shape ", t.sizes(), ", expected ", shape);
+    TORCH_CHECK(aligned16(t) && t.device() == pixels.device(), W, ": ", name, " misaligned or on another device");
+}
+
+// -> (ctx [N, d], z [N, 2, d], lse [N, 2], Q [N, d]); the last three are what the backward needs
+std::vector<at::Tensor> lava_xattn_fwd(at::Tensor pixels, at::Tensor q, at::Tensor ln_w, at::Tensor ln_b, double eps,
+                                       at::Tensor in_w, at::Tensor in_b) {
+    const char* W = "lava_xattn_fwd";
+    check_lava_xattn(W, pixels, ln_w, ln_b, in_w, in_b);
+    const int64_t N = pixels.size(0), S = pixels.size(1), d = pixels.size(2), C = rt1_lava_xattn_chunks(S);
+    check_lava_frames(W, q, "q", pixels, {d});
+    const auto o = pixels.options();
+    at::Tensor ctx = at::empty({N, d}, o), z = at::empty({N, 2, d}, o), lse = at::empty({N, 2}, o),
+               Q = at::empty({N, d}, o), u = at::empty({N, 2, d}, o), fc = at::empty({N, 8}, o),
+               pm = at::empty({N, C, 2}, o), pl = at::empty({N, C, 2}, o), pz = at::empty({N, C, 2, d}, o);
+    check_launch(rt1_lava_xattn_fwd(pixels.data_ptr<float>(), q.data_ptr<float>(), ln_w.data_ptr<float>(),
+                                    ln_b.data_ptr<float>(), (float)eps, in_w.data_ptr<float>(),
+                                    in_b.data_ptr<float>(), N, S, Q.data_ptr<float>(), u.data_ptr<float>(),
+                                    fc.data_ptr<float>(), pm.data_ptr<float>(), pl.data_ptr<float>(),
+                                    pz.data_ptr<float>(), z.data_ptr<float>(), lse.data_ptr<float>(),
+                                    ctx.data_ptr<float>(), cur_stream()),
+                 W);
+    return {ctx, z, lse, Q};
+}
+
+// -> (dpix [N, S, d], dq [N, d], dQ [N, d], u, w, e [N, 2, d]); the sums over frames are the caller's
+std::vector<at::Tensor> lava_xattn_bwd(at::Tensor dctx, at::Tensor pixels, at::Tensor Q, at::Tensor z, at::Tensor lse,
+                                       at::Tensor ln_w, at::Tensor ln_b, double eps, at::Tensor in_w,
+                                       at::Tensor in_b) {
+    const char* W = "lava_xattn_bwd";
+    check_lava_xattn(W, pixels, ln_w, ln_b, in_w, in_b);
+    const int64_t N = pixels.size(0), S = pixels.size(1), d = pixels.size(2), C = rt1_lava_xattn_chunks(S);
+    check_lava_frames(W, dctx, "dctx", pixels, {d});
+    check_lava_frames(W, Q, "Q", pixels, {d});
+    check_lava_frames(W, z, "z", pixels, {2, d});
+    check_lava_frames(W, lse, "lse", pixels, {2});
+    const auto o = pixels.options();
+    at::Tensor dpix = at::empty({N, S, d}, o), dq = at::empty({N, d}, o), dQ = at::empty({N, d}, o),
+               u = at::empty({N, 2, d}, o), w = at::empty({N, 2, d}, o), e = at::empty({N, 2, d}, o),
+               fc = at::empty({N, 8}, o), pe = at::empty({N, C, 2, d}, o);
+    check_launch(rt1_lava_xattn_bwd(dctx.data_ptr<float>(), pixels.data_ptr<float>(), Q.data_ptr<float>(),
+                                    z.data_ptr<float>(), lse.data_ptr<float>(), ln_w.data_ptr<float>(),
+                                    ln_b.data_ptr<float>(), (float)eps, in_w.data_ptr<float>(),
+                                    in_b.data_ptr<float>(), N, S, u.data_ptr<float>(), w.data_ptr<float>(),
+                                    fc.data_ptr<float>(), pe.data_ptr<float>(), dpix.data_ptr<float>(),
+                                    e.data_ptr<float>(), dQ.data_ptr<float>(), dq.data_ptr<float>(), cur_stream()),
+                 W);
+    return {dpix, dq, dQ, u, w, e};
+}
+
+bool lava_xattn_supported(int64_t d, int64_t heads) {
+    return d > 0 && d <= INT32_MAX && heads > 0 && heads <= INT32_MAX && rt1_lava_xattn_supported((int)d, (int)heads);
+}
+
 // For tools/bench_lamb.py only: ONE of the three launches of flat_lamb_dev (kernel 1 moments, 2 trust, 3 apply) on the
 // same checked arguments, so that each kernel can be timed.  Not an optimizer step: kernel 3 alone applies whatever
 // trust holds.
@@ -1787,6 +1868,11 @@ PYBIND11_MODULE(_rt1_hip, m) {
     m.def("flat_lamb_dev", &flat_lamb_dev,
           "LAMB (layer-wise trust ratios) over flat fp32 buffers in three launches, every form of flat_adam_dev");
     m.def("lamb_kernel_alone", &lamb_kernel_alone, "one of flat_lamb_dev's three launches, for timing (not a step)");
+    m.def("lava_xattn_supported", &lava_xattn_supported, "whether lava_xattn_fwd / bwd serve (d_model, heads)");
+    m.def("lava_xattn_fwd", &lava_xattn_fwd,
+          "LAVA one-query cross attention, LayerNorm + K/V + softmax folded: -> (ctx, z, lse, Q)");
+    m.def("lava_xattn_bwd", &lava_xattn_bwd,
+          "its backward: -> (dpix, dq, dQ, u, w, e); parameter gradients are sums over frames of these");
     m.def("lr_schedule_dev", &lr_schedule_dev,
           "per-step lr schedule on the device: state[1] / group_state[g][0] <- lr_base[g] * f(effective Adam step)");
     m.def("gradnorm_partials", &gradnorm_partials, "fp64 partial sums grad_sumsq writes for n floats");

@@ -55,6 +55,26 @@ int rt1_lamb_apply(float* p, const float* m, const float* v, int64_t n, const fl
                    const float* trust, const uint16_t* chunk_tensor, int nT, float beta1, float beta2, float eps,
                    float weight_decay, float one_minus_decay, int warmup, hipStream_t stream);
 
+// lavaxattn.hip: LAVA pixel-language cross attention with one query per frame (d = 128, 2 heads), LayerNorm of the
+// pixels, K / V projections and the attention folded into one streamed pass over pix fp32[N, S, 128]; all fp32.
+// g, b, eps: the pixel LayerNorm; W fp32[384, 128], bias fp32[384]: MultiheadAttention's in_proj; C =
+// rt1_lava_xattn_chunks(S) row chunks per frame.  Three launches each (per-frame prologue, frames x chunks, per-frame
+// combine in chunk order), no atomics.
+//   fwd  q fp32[N, 128] -> ctx fp32[N, 128] (the heads' context, before out_proj); saves Q [N, 128], z [N, 2, 128]
+//        (sum_j a_j x^_j), lse [N, 2].  Workspaces: u [N, 2, 128], fc [N, 8], pm / pl [N, C, 2], pz [N, C, 2, 128].
+//   bwd  dctx [N, 128] and the saved Q, z, lse -> dpix [N, S, 128], dq [N, 128], and per frame dQ [N, 128],
+//        u, w, e [N, 2, 128] from which the caller forms the sums over frames (the parameter gradients).  Workspaces:
+//        fc [N, 8], pe [N, C, 2, 128].
+int rt1_lava_xattn_supported(int d, int H);
+int64_t rt1_lava_xattn_chunks(int64_t S);
+int rt1_lava_xattn_fwd(const float* pix, const float* q, const float* g, const float* b, float eps, const float* W,
+                       const float* bias, int64_t N, int64_t S, float* Q, float* u, float* fc, float* pm, float* pl,
+                       float* pz, float* z, float* lse, float* ctx, hipStream_t stream);
+int rt1_lava_xattn_bwd(const float* dctx, const float* pix, const float* Q, const float* z, const float* lse,
+                       const float* g, const float* b, float eps, const float* W, const float* bias, int64_t N,
+                       int64_t S, float* u, float* w, float* fc, float* pe, float* dpix, float* e, float* dQ, float* dq,
+                       hipStream_t stream);
+
 // gradnorm.hip (deterministic global gradient norm -> clip_state fp32[8] = {norm, coef, ok, skipped steps, clipped
 // steps, consecutive skipped steps, 0, 0}; rt1_gradnorm_partials: workgroups / fp64 partials for n floats, a function
 // of n alone, 0 for n <= 0)

@@ -41,6 +41,7 @@ class LavaConfig:
     height: int = 180
     width: int = 320
     dropout: float = 0.1
+    backend: str = "torch"                    # pixel-language attention: torch | hip | auto (ops/lava_attention.py)
 
 
 def _dense(i: int, o: int) -> nn.Linear:
@@ -110,14 +111,22 @@ class ConvMaxpoolEncoder(nn.Module):
 class CrossLayer(nn.Module):
     """Pre-norm language(query) -> pixels(key/value) attention with a residual on the language path."""
 
-    def __init__(self, d: int, heads: int, dff: int, dropout: float):
+    def __init__(self, d: int, heads: int, dff: int, dropout: float, backend: str = "torch"):
         super().__init__()
         self.ln_pix, self.ln_lang, self.ln_ffn = nn.LayerNorm(d), nn.LayerNorm(d), nn.LayerNorm(d)
         self.attn = nn.MultiheadAttention(d, heads, batch_first=True)
         self.ff1, self.ff2 = _dense(d, dff), _dense(dff, dff)
         self.drop = nn.Dropout(dropout)
+        self.backend = backend                                           # "torch" or "hip", already resolved
 
     def forward(self, pix, lang):
+        if self.backend == "hip":
+            # pixel LayerNorm, K / V projections and the one-query attention in one pass over pix (lavaxattn.hip);
+            # the out-projection, dropout and FFN are [N, d] work and stay as they are
+            from ..ops.lava_attention import cross_attention
+            ctx = cross_attention(pix, self.ln_lang(lang)[:, 0], self.ln_pix, self.attn)
+            x3 = lang + self.drop(self.attn.out_proj(ctx)[:, None])
+            return x3 + self.drop(self.ff2(F.relu(self.ff1(self.ln_ffn(x3)))))
         p, q = self.ln_pix(pix), self.ln_lang(lang)
         x3 = lang + self.drop(self.attn(q, p, p, need_weights=False)[0])
         return x3 + self.drop(self.ff2(F.relu(self.ff1(self.ln_ffn(x3)))))
@@ -163,7 +172,11 @@ class SequenceLAVMSE(nn.Module):
         self.visual_proj = nn.ModuleDict({str(i): _dense(self.image_encoder.channels[i], d)
                                           for i in cfg.pyramid_fuse_layers})
         self.lang_proj = _dense(cfg.lang_dim, d)
-        self.cross = nn.ModuleList(CrossLayer(d, 2, d, cfg.dropout) for _ in range(cfg.num_layers))
+        self.backend = "torch"
+        if cfg.backend != "torch":
+            from ..ops.lava_attention import resolve_backend
+            self.backend = resolve_backend(cfg.backend, d, 2)            # ValueError when hip cannot be served
+        self.cross = nn.ModuleList(CrossLayer(d, 2, d, cfg.dropout, self.backend) for _ in range(cfg.num_layers))
         self.fuse_norm = nn.LayerNorm(d)
         self.temporal_in = _dense(d, d)
         self.temporal = nn.ModuleList(SelfLayer(d, cfg.num_heads, d, cfg.dropout)
@@ -196,7 +209,7 @@ class SequenceLAVMSE(nn.Module):
             v = self.visual_proj[str(i)](f.flatten(2).transpose(1, 2)) * math.sqrt(d)
             sent.append(v + self._pos(h, w, v.device))
         pixels = self.drop(torch.cat(sent, dim=1))                      # (N, sum hw, d)
-        q = self.drop(self.lang_proj(lang.reshape(b * t, -1).float()) * math.sqrt(d))[:, None]
+        q = self.drop(self.lang_proj(lang.reshape(b * t, -1).to(self.lang_proj.weight.dtype)) * math.sqrt(d))[:, None]
         for layer in self.cross:
             q = layer(pixels, q)
         z = self.fuse_norm(q[:, 0]).reshape(b, t, d)

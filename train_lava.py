@@ -42,6 +42,8 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--network", choices=["lava", "pixel"], default="lava",
                     help="SequenceLAVMSE (reference default) or PixelLangMSE (networks/pixel.py)")
+    ap.add_argument("--backend", choices=["torch", "hip", "auto"], default="torch",
+                    help="pixel-language cross attention: eager torch, the folded HIP kernels, or hip when available")
     ap.add_argument("--freeze_keys", nargs="*", default=[], help="parameter-name substrings to keep frozen")
     ap.add_argument("--pretrained", nargs="*", default=[],
                     help="PATH:CKPT_PREFIX=MODEL_PREFIX[,CKPT_PREFIX=MODEL_PREFIX] pretrained checkpoints")
@@ -69,7 +71,7 @@ def main(argv=None):
     if ctx.is_main:
         stats = normalization.compute_dataset_statistics(sim_demos.action_batches(ds), num_samples=len(ds))
     stats = normalization.broadcast_stats(stats)
-    cfg = LavaConfig(sequence_length=a.sequence_length, d_model=a.d_model)
+    cfg = LavaConfig(sequence_length=a.sequence_length, d_model=a.d_model, backend=a.backend)
     augment = None
     if a.augment:
         from pytorch_rt1_for_distributed_training_amd.data.augment import BCAugment
