@@ -451,6 +451,115 @@ bool lava_xattn_supported(int64_t d, int64_t heads) {
     return d > 0 && d <= INT32_MAX && heads > 0 && heads <= INT32_MAX && rt1_lava_xattn_supported((int)d, (int)heads);
 }
 
+// LAVA image-encoder stage conv3x3 + ReLU + maxpool2 (csrc/kernels/lavaconv.hip).  x is NHWC: bf16 activations, or
+// for the first stage the frames, uint8 or fp32 [N, H, W, 3].  weight / bias are the nn.Conv2d parameters (fp32
+// [cout, cin, 3, 3] / [cout]); the KB-sized bf16 packs the kernels read are formed here.
+uint16_t* bf16_ptr(const at::Tensor& t) { return reinterpret_cast<uint16_t*>(t.data_ptr()); }
+
+int lava_conv_x_kind(const char* W, const at::Tensor& x, int64_t cin) {
+    TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 4 && x.size(3) == cin, W,
+                ": x must be a contiguous GPU tensor [N, H, W, ", cin, "]");
+    TORCH_CHECK(x.size(0) >= 1 && x.size(1) >= 2 && x.size(2) >= 2, W, ": x needs N >= 1 and H, W >= 2");
+    if (cin == 3) {                       // read value by value: no alignment asked of the frames
+        TORCH_CHECK(x.scalar_type() == at::kByte || x.scalar_type() == at::kFloat, W,
+                    ": the frames must be uint8 or float32, got ", x.scalar_type());
+        return x.scalar_type() == at::kByte ? 1 : 2;
+    }
+    TORCH_CHECK(x.scalar_type() == at::kBFloat16, W, ": x has dtype ", x.scalar_type(), ", expected bfloat16");
+    TORCH_CHECK(aligned16(x), W, ": x must be 16-byte aligned");
+    return 0;
+}
+
+void check_lava_conv_weight(const char* W, const at::Tensor& weight, const at::Tensor& dev_of) {
+    check_dev(weight, "weight", at::kFloat);
+    TORCH_CHECK(weight.dim() == 4 && weight.size(2) == 3 && weight.size(3) == 3, W, ": weight must be [cout, cin, 3, 3]");
+    TORCH_CHECK(weight.size(0) <= INT32_MAX && weight.size(1) <= INT32_MAX &&
+                    rt1_lava_conv_supported((int)weight.size(1), (int)weight.size(0)),
+                W, ": (cin, cout) = (", weight.size(1), ", ", weight.size(0),
+                ") is not served ((3, 32), (32, 64), (64, 128), (128, 256))");
+    TORCH_CHECK(weight.device() == dev_of.device(), W, ": tensors on different devices");
+}
+
+// the pooled pair (dy bf16, idx uint8) [N, H / 2, W / 2, cout] of a stage whose input is [N, H, W, *]
+void check_lava_conv_pooled(const char* W, const at::Tensor& dy, const at::Tensor& idx, int64_t N, int64_t H,
+                            int64_t Wd, int64_t cout) {
+    check_dev(dy, "dy", at::kBFloat16);
+    check_dev(idx, "idx", at::kByte);
+    const std::vector<int64_t> shape{N, H / 2, Wd / 2, cout};
+    TORCH_CHECK(dy.sizes() == at::IntArrayRef(shape) && idx.sizes() == at::IntArrayRef(shape), W,
+                ": dy / idx have shapes ", dy.sizes(), " / ", idx.sizes(), ", expected ", shape);
+    TORCH_CHECK(aligned16(dy) && aligned16(idx) && dy.device() == idx.device(), W,
+                ": dy / idx misaligned or on different devices");
+}
+
+// -> (y bf16, idx uint8) [N, H / 2, W / 2, cout]
+std::vector<at::Tensor> lava_conv_fwd(at::Tensor x, at::Tensor weight, at::Tensor bias) {
+    const char* W = "lava_conv_fwd";
+    check_lava_conv_weight(W, weight, x);
+    const int64_t cout = weight.size(0), cin = weight.size(1);
+    const int kind = lava_conv_x_kind(W, x, cin);
+    check_dev(bias, "bias", at::kFloat);
+    TORCH_CHECK(bias.numel() == cout && bias.device() == x.device(), W, ": bias must be [cout] on x's device");
+    const int64_t N = x.size(0), H = x.size(1), Wd = x.size(2);
+    at::Tensor wp = weight.permute({2, 3, 1, 0}).contiguous().to(at::kBFloat16);            // [9][cin][cout]
+    at::Tensor y = at::empty({N, H / 2, Wd / 2, cout}, x.options().dtype(at::kBFloat16));
+    at::Tensor idx = at::empty({N, H / 2, Wd / 2, cout}, x.options().dtype(at::kByte));
+    check_launch(rt1_lava_conv_fwd(x.data_ptr(), kind, bf16_ptr(wp), bias.data_ptr<float>(), N, H, Wd, (int)cin,
+                                   (int)cout, bf16_ptr(y), idx.data_ptr<uint8_t>(), cur_stream()),
+                 W);
+    return {y, idx};
+}
+
+// -> dx bf16 [N, H, W, cin]; (H, W) is the stage's input grid (the pooled grid does not tell an odd side)
+at::Tensor lava_conv_dgrad(at::Tensor dy, at::Tensor idx, at::Tensor weight, int64_t H, int64_t Wd) {
+    const char* W = "lava_conv_dgrad";
+    check_lava_conv_weight(W, weight, dy);
+    const int64_t cout = weight.size(0), cin = weight.size(1);
+    TORCH_CHECK(cin != 3, W, ": the frames have no gradient");
+    TORCH_CHECK(dy.dim() == 4 && H >= 2 && Wd >= 2, W, ": dy must be [N, H / 2, W / 2, cout]");
+    const int64_t N = dy.size(0);
+    check_lava_conv_pooled(W, dy, idx, N, H, Wd, cout);
+    at::Tensor wd = weight.flip({2, 3}).permute({2, 3, 0, 1}).contiguous().to(at::kBFloat16);   // [9][cout][cin]
+    at::Tensor dx = at::empty({N, H, Wd, cin}, dy.options());
+    check_launch(rt1_lava_conv_dgrad(bf16_ptr(dy), idx.data_ptr<uint8_t>(), bf16_ptr(wd), N, H, Wd, (int)cin,
+                                     (int)cout, bf16_ptr(dx), cur_stream()),
+                 W);
+    return dx;
+}
+
+// -> (dW fp32 [cout, cin, 3, 3], db fp32 [cout])
+std::vector<at::Tensor> lava_conv_wgrad(at::Tensor x, at::Tensor dy, at::Tensor idx) {
+    const char* W = "lava_conv_wgrad";
+    TORCH_CHECK(x.dim() == 4 && dy.dim() == 4, W, ": x must be [N, H, W, cin] and dy [N, H / 2, W / 2, cout]");
+    const int64_t cin = x.size(3), cout = dy.size(3);
+    TORCH_CHECK(cin <= INT32_MAX && cout <= INT32_MAX && rt1_lava_conv_supported((int)cin, (int)cout), W,
+                ": (cin, cout) = (", cin, ", ", cout, ") is not served");
+    const int kind = lava_conv_x_kind(W, x, cin);
+    const int64_t N = x.size(0), H = x.size(1), Wd = x.size(2);
+    check_lava_conv_pooled(W, dy, idx, N, H, Wd, cout);
+    TORCH_CHECK(dy.device() == x.device(), W, ": tensors on different devices");
+    const int64_t P = rt1_lava_conv_wgrad_partials(N, H, Wd, (int)cin, (int)cout);
+    TORCH_CHECK(P >= 1, W, ": the shape is not served");
+    const auto o = x.options().dtype(at::kFloat);
+    at::Tensor part = at::empty({P, 9 * cin, cout}, o), dbpart = at::empty({P, cout}, o);
+    at::Tensor dW = at::empty({cout, cin, 3, 3}, o), db = at::empty({cout}, o);
+    check_launch(rt1_lava_conv_wgrad(x.data_ptr(), kind, bf16_ptr(dy), idx.data_ptr<uint8_t>(), N, H, Wd, (int)cin,
+                                     (int)cout, part.data_ptr<float>(), dbpart.data_ptr<float>(),
+                                     dW.data_ptr<float>(), db.data_ptr<float>(), cur_stream()),
+                 W);
+    return {dW, db};
+}
+
+bool lava_conv_supported(int64_t cin, int64_t cout) {
+    return cin > 0 && cin <= INT32_MAX && cout > 0 && cout <= INT32_MAX && rt1_lava_conv_supported((int)cin, (int)cout);
+}
+
+int64_t lava_conv_wgrad_partials(int64_t N, int64_t H, int64_t W, int64_t cin, int64_t cout) {
+    return lava_conv_supported(cin, cout) ? rt1_lava_conv_wgrad_partials(N, H, W, (int)cin, (int)cout) : 0;
+}
+
+std::vector<int64_t> lava_conv_tile() { return {rt1_lava_conv_tile_h(), rt1_lava_conv_tile_w()}; }
+
 // For tools/bench_lamb.py only: ONE of the three launches of flat_lamb_dev (kernel 1 moments, 2 trust, 3 apply) on the
 // same checked arguments, so that each kernel can be timed.  Not an optimizer step: kernel 3 alone applies whatever
 // trust holds.
@@ -1873,6 +1982,14 @@ PYBIND11_MODULE(_rt1_hip, m) {
           "LAVA one-query cross attention, LayerNorm + K/V + softmax folded: -> (ctx, z, lse, Q)");
     m.def("lava_xattn_bwd", &lava_xattn_bwd,
           "its backward: -> (dpix, dq, dQ, u, w, e); parameter gradients are sums over frames of these");
+    m.def("lava_conv_supported", &lava_conv_supported, "whether the lava_conv kernels serve (cin, cout)");
+    m.def("lava_conv_tile", &lava_conv_tile, "(rows, columns) of the conv tile of one workgroup");
+    m.def("lava_conv_wgrad_partials", &lava_conv_wgrad_partials,
+          "workgroup partials lava_conv_wgrad writes for (N, H, W, cin, cout); 0 for an unserved shape");
+    m.def("lava_conv_fwd", &lava_conv_fwd,
+          "maxpool2(relu(conv3x3_same(x NHWC, weight) + bias)) -> (y bf16, idx uint8: 0..3 winner, 4 dead)");
+    m.def("lava_conv_dgrad", &lava_conv_dgrad, "its data gradient from the pooled (dy, idx): -> dx bf16 [N, H, W, cin]");
+    m.def("lava_conv_wgrad", &lava_conv_wgrad, "its weight and bias gradients from x and the pooled (dy, idx): fp32");
     m.def("lr_schedule_dev", &lr_schedule_dev,
           "per-step lr schedule on the device: state[1] / group_state[g][0] <- lr_base[g] * f(effective Adam step)");
     m.def("gradnorm_partials", &gradnorm_partials, "fp64 partial sums grad_sumsq writes for n floats");

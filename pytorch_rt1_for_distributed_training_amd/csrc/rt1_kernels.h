@@ -75,6 +75,27 @@ int rt1_lava_xattn_bwd(const float* dctx, const float* pix, const float* Q, cons
                        int64_t S, float* u, float* w, float* fc, float* pe, float* dpix, float* e, float* dQ, float* dq,
                        hipStream_t stream);
 
+// lavaconv.hip: one LAVA image-encoder stage, y = maxpool2(relu(conv3x3_same(x, W) + b)) with VALID pooling, as
+// implicit-GEMM MFMA kernels; (cin, cout) in {(3, 32), (32, 64), (64, 128), (128, 256)}, H, W >= 2.  Activations and
+// their gradients are NHWC bf16 (raw uint16_t here), the pooled grid is [H / 2, W / 2].  x_kind: 0 = bf16
+// activations (cin >= 32), 1 = uint8 frames (/255), 2 = fp32 frames (cin = 3).
+//   fwd    wp bf16 [9][cin][cout], bias fp32 [cout] -> y bf16 and idx uint8 [N, H/2, W/2, cout]; idx 0..3 = the
+//          winning window position (row-major, ties to the lowest), 4 = dead (window max <= 0, y = 0)
+//   dgrad  (dy, idx) and wd bf16 [9][cout][cin] (flipped, transposed) -> dx bf16 [N, H, W, cin]; cin >= 32
+//   wgrad  x, (dy, idx) -> dW fp32 [cout][cin][3][3], db fp32 [cout]; workspaces part fp32 [P][9 * cin][cout] and
+//          dbpart fp32 [P][cout], P = rt1_lava_conv_wgrad_partials(...); partials added in a fixed order, no atomics
+int rt1_lava_conv_supported(int cin, int cout);
+int rt1_lava_conv_tile_h();
+int rt1_lava_conv_tile_w();
+int rt1_lava_conv_fwd(const void* x, int x_kind, const uint16_t* wp, const float* bias, int64_t N, int64_t H,
+                      int64_t W, int cin, int cout, uint16_t* y, uint8_t* idx, hipStream_t stream);
+int rt1_lava_conv_dgrad(const uint16_t* dy, const uint8_t* idx, const uint16_t* wd, int64_t N, int64_t H, int64_t W,
+                        int cin, int cout, uint16_t* dx, hipStream_t stream);
+int64_t rt1_lava_conv_wgrad_partials(int64_t N, int64_t H, int64_t W, int cin, int cout);
+int rt1_lava_conv_wgrad(const void* x, int x_kind, const uint16_t* dy, const uint8_t* idx, int64_t N, int64_t H,
+                        int64_t W, int cin, int cout, float* part, float* dbpart, float* dW, float* db,
+                        hipStream_t stream);
+
 // gradnorm.hip (deterministic global gradient norm -> clip_state fp32[8] = {norm, coef, ok, skipped steps, clipped
 // steps, consecutive skipped steps, 0, 0}; rt1_gradnorm_partials: workgroups / fp64 partials for n floats, a function
 // of n alone, 0 for n <= 0)

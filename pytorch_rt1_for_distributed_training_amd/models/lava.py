@@ -42,6 +42,7 @@ class LavaConfig:
     width: int = 320
     dropout: float = 0.1
     backend: str = "torch"                    # pixel-language attention: torch | hip | auto (ops/lava_attention.py)
+    encoder_backend: str = "torch"            # conv-maxpool image encoder: torch | hip | auto (ops/lava_conv.py)
 
 
 def _dense(i: int, o: int) -> nn.Linear:
@@ -90,7 +91,7 @@ class ConvMaxpoolEncoder(nn.Module):
     """Feature pyramid: 4 x (conv3x3 SAME + ReLU + maxpool2), then one more maxpool (5 levels).  The convs take
     Flax ``nn.Conv``'s default init like the reference's (``language_table/train/networks/lava.py:43``)."""
 
-    def __init__(self, channels: Sequence[int] = (32, 64, 128, 256)):
+    def __init__(self, channels: Sequence[int] = (32, 64, 128, 256), backend: str = "torch"):
         super().__init__()
         convs, cin = [], 3
         for c in channels:
@@ -98,8 +99,23 @@ class ConvMaxpoolEncoder(nn.Module):
             cin = c
         self.convs = nn.ModuleList(convs)
         self.channels = list(channels) + [channels[-1]]
+        self.backend = "torch"
+        if backend != "torch":
+            from ..ops.lava_conv import resolve_backend
+            stages = tuple(zip([3] + list(channels[:-1]), channels))
+            self.backend = resolve_backend(backend, stages)              # ValueError when hip cannot be served
 
-    def forward(self, x):                                                # x (N, 3, H, W)
+    def forward(self, x):                  # torch: x (N, 3, H, W); hip: the frames (N, H, W, 3), uint8 or fp32
+        if self.backend == "hip":
+            # conv + bias + ReLU + pool per stage in one MFMA kernel, NHWC bf16 between the stages (lavaconv.hip);
+            # a level is the logical (N, C, h, w) fp32 view of that storage
+            from ..ops.lava_conv import conv_relu_pool
+            levels = []
+            for conv in self.convs:
+                x = conv_relu_pool(x, conv)
+                levels.append(x.permute(0, 3, 1, 2).float())
+            levels.append(F.max_pool2d(levels[-1], 2))
+            return levels
         levels = []
         for conv in self.convs:
             x = F.max_pool2d(F.relu(conv(x)), 2)
@@ -168,7 +184,7 @@ class SequenceLAVMSE(nn.Module):
         super().__init__()
         self.cfg = cfg
         d = cfg.d_model
-        self.image_encoder = ConvMaxpoolEncoder()
+        self.image_encoder = ConvMaxpoolEncoder(backend=cfg.encoder_backend)
         self.visual_proj = nn.ModuleDict({str(i): _dense(self.image_encoder.channels[i], d)
                                           for i in cfg.pyramid_fuse_layers})
         self.lang_proj = _dense(cfg.lang_dim, d)
@@ -197,9 +213,13 @@ class SequenceLAVMSE(nn.Module):
     def encode(self, rgb: torch.Tensor, lang: torch.Tensor) -> torch.Tensor:
         b, t = rgb.shape[:2]
         x = rgb.reshape(b * t, *rgb.shape[2:])
-        if x.dtype == torch.uint8:
-            x = x.float() / 255.0
-        x = x.permute(0, 3, 1, 2).contiguous()                         # NHWC -> NCHW
+        if self.image_encoder.backend == "hip":
+            if x.dtype != torch.uint8:
+                x = x.float()
+        else:                                                           # the kernels read NHWC and fuse the /255
+            if x.dtype == torch.uint8:
+                x = x.float() / 255.0
+            x = x.permute(0, 3, 1, 2).contiguous()                     # NHWC -> NCHW
         levels = self.image_encoder(x)
         d = self.cfg.d_model
         sent = []

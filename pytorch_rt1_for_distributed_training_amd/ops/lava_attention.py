@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import torch
 
+from ._backend import resolve
 from ._ext import available, load
 
 HEADS = 2          # CrossLayer's head count
@@ -22,20 +23,8 @@ def supported(d_model: int, heads: int = HEADS) -> bool:
 def resolve_backend(backend: str, d_model: int, heads: int = HEADS) -> str:
     """``torch | hip | auto`` -> ``torch | hip``.  ``hip`` needs a GPU, the extension and a supported shape and says
     which is missing; ``auto`` is ``hip`` exactly when all three hold."""
-    if backend not in ("torch", "hip", "auto"):
-        raise ValueError(f"backend is {backend!r}, expected 'torch', 'hip' or 'auto'")
-    if backend == "torch":
-        return backend
-    cuda = torch.cuda.is_available()
-    if backend == "auto":
-        return "hip" if (cuda and supported(d_model, heads)) else "torch"
-    if not cuda:
-        raise ValueError("the hip backend needs a GPU")
-    if not available():
-        raise ValueError("the hip backend needs the HIP extension (python build.py)")
-    if not supported(d_model, heads):
-        raise ValueError(f"the hip backend does not serve d_model={d_model}, heads={heads} (d_model=128, heads=2)")
-    return backend
+    return resolve(backend, lambda: supported(d_model, heads),
+                   f"d_model={d_model}, heads={heads} (d_model=128, heads=2)")
 
 
 class LavaCrossAttnFn(torch.autograd.Function):

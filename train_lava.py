@@ -44,6 +44,9 @@ def main(argv=None):
                     help="SequenceLAVMSE (reference default) or PixelLangMSE (networks/pixel.py)")
     ap.add_argument("--backend", choices=["torch", "hip", "auto"], default="torch",
                     help="pixel-language cross attention: eager torch, the folded HIP kernels, or hip when available")
+    ap.add_argument("--encoder_backend", choices=["torch", "hip", "auto"], default="torch",
+                    help="conv-maxpool image encoder: eager torch, the fused conv+ReLU+pool HIP kernels, or hip when "
+                         "available")
     ap.add_argument("--freeze_keys", nargs="*", default=[], help="parameter-name substrings to keep frozen")
     ap.add_argument("--pretrained", nargs="*", default=[],
                     help="PATH:CKPT_PREFIX=MODEL_PREFIX[,CKPT_PREFIX=MODEL_PREFIX] pretrained checkpoints")
@@ -71,7 +74,8 @@ def main(argv=None):
     if ctx.is_main:
         stats = normalization.compute_dataset_statistics(sim_demos.action_batches(ds), num_samples=len(ds))
     stats = normalization.broadcast_stats(stats)
-    cfg = LavaConfig(sequence_length=a.sequence_length, d_model=a.d_model, backend=a.backend)
+    cfg = LavaConfig(sequence_length=a.sequence_length, d_model=a.d_model, backend=a.backend,
+                     encoder_backend=a.encoder_backend)
     augment = None
     if a.augment:
         from pytorch_rt1_for_distributed_training_amd.data.augment import BCAugment
