@@ -560,6 +560,126 @@ int64_t lava_conv_wgrad_partials(int64_t N, int64_t H, int64_t W, int64_t cin, i
 
 std::vector<int64_t> lava_conv_tile() { return {rt1_lava_conv_tile_h(), rt1_lava_conv_tile_w()}; }
 
+// LAVA visual sentence (csrc/kernels/lavasent.hip).  L2 / L3 are the encoder's NHWC bf16 stage outputs, the weights
+// the three nn.Linear parameters (fp32 [128, C]); the KB-sized bf16 packs the kernels read are formed here.
+struct SentShape {
+    int64_t N, h2, w2, h3, w3, S;
+};
+
+SentShape check_lava_sentence_levels(const char* W, const at::Tensor& L2, const at::Tensor& L3) {
+    check_dev(L2, "L2", at::kBFloat16);
+    check_dev(L3, "L3", at::kBFloat16);
+    TORCH_CHECK(L2.dim() == 4 && L3.dim() == 4 && L2.size(3) == 128 && L3.size(3) == 256 && L2.size(0) == L3.size(0),
+                W, ": L2 / L3 must be [N, h2, w2, 128] / [N, h3, w3, 256], got ", L2.sizes(), " / ", L3.sizes());
+    TORCH_CHECK(aligned16(L2) && aligned16(L3) && L2.device() == L3.device(), W,
+                ": L2 / L3 misaligned or on different devices");
+    SentShape s{L2.size(0), L2.size(1), L2.size(2), L3.size(1), L3.size(2), 0};
+    int64_t P[3];
+    TORCH_CHECK(rt1_lava_sentence_wgrad_partials(s.N, s.h2, s.w2, s.h3, s.w3, P), W,
+                ": the shape is not served (N, h2, w2 >= 1, h3, w3 >= 2, N * S < 2^31)");
+    s.S = s.h2 * s.w2 + s.h3 * s.w3 + (s.h3 / 2) * (s.w3 / 2);
+    return s;
+}
+
+void check_lava_sentence_weights(const char* W, const at::Tensor& w2, const at::Tensor& w3, const at::Tensor& w4,
+                                 const at::Tensor& dev_of) {
+    const at::Tensor* ws[3] = {&w2, &w3, &w4};
+    for (int l = 0; l < 3; ++l) {
+        check_dev(*ws[l], "weight", at::kFloat);
+        TORCH_CHECK(ws[l]->dim() == 2 && ws[l]->size(0) == 128 && ws[l]->size(1) == (l == 0 ? 128 : 256) &&
+                        ws[l]->device() == dev_of.device(),
+                    W, ": weight of level ", l + 2, " must be [128, ", l == 0 ? 128 : 256, "] on the levels' device");
+    }
+}
+
+void check_lava_sentence_dpix(const char* W, const at::Tensor& dpix, const SentShape& s, const at::Tensor& dev_of,
+                              double p, int64_t seed) {
+    check_dev(dpix, "dpix", at::kFloat);
+    const std::vector<int64_t> shape{s.N, s.S, 128};
+    TORCH_CHECK(dpix.sizes() == at::IntArrayRef(shape) && aligned16(dpix) && dpix.device() == dev_of.device(), W,
+                ": dpix must be ", shape, " , 16-byte aligned, on the levels' device; got ", dpix.sizes());
+    TORCH_CHECK(p >= 0.0 && p < 1.0 && seed >= 0 && seed <= (int64_t)UINT32_MAX, W,
+                ": needs 0 <= p < 1 and a 32-bit seed");
+}
+
+at::Tensor lava_sentence_fwd(at::Tensor L2, at::Tensor L3, at::Tensor w2, at::Tensor b2, at::Tensor w3, at::Tensor b3,
+                             at::Tensor w4, at::Tensor b4, at::Tensor pos, double p, int64_t seed) {
+    const char* W = "lava_sentence_fwd";
+    const SentShape s = check_lava_sentence_levels(W, L2, L3);
+    check_lava_sentence_weights(W, w2, w3, w4, L2);
+    for (const at::Tensor* b : {&b2, &b3, &b4}) {
+        check_dev(*b, "bias", at::kFloat);
+        TORCH_CHECK(b->numel() == 128 && aligned16(*b) && b->device() == L2.device(), W,
+                    ": a bias must be [128], 16-byte aligned, on the levels' device");
+    }
+    check_dev(pos, "pos", at::kFloat);
+    const std::vector<int64_t> pshape{s.S, 128};
+    TORCH_CHECK(pos.sizes() == at::IntArrayRef(pshape) && aligned16(pos) && pos.device() == L2.device(), W,
+                ": pos must be ", pshape, ", 16-byte aligned, on the levels' device; got ", pos.sizes());
+    TORCH_CHECK(p >= 0.0 && p < 1.0 && seed >= 0 && seed <= (int64_t)UINT32_MAX, W,
+                ": needs 0 <= p < 1 and a 32-bit seed");
+    at::Tensor p2 = w2.to(at::kBFloat16), p3 = w3.to(at::kBFloat16), p4 = w4.to(at::kBFloat16);      // [128][K]
+    at::Tensor pix = at::empty({s.N, s.S, 128}, L2.options().dtype(at::kFloat));
+    check_launch(rt1_lava_sentence_fwd(bf16_ptr(L2), bf16_ptr(L3), bf16_ptr(p2), bf16_ptr(p3), bf16_ptr(p4),
+                                       b2.data_ptr<float>(), b3.data_ptr<float>(), b4.data_ptr<float>(),
+                                       pos.data_ptr<float>(), s.N, s.h2, s.w2, s.h3, s.w3, (float)p, (uint32_t)seed,
+                                       pix.data_ptr<float>(), cur_stream()),
+                 W);
+    return pix;
+}
+
+// -> (dL2 bf16 [N, h2, w2, 128], dL3 bf16 [N, h3, w3, 256])
+std::vector<at::Tensor> lava_sentence_dgrad(at::Tensor dpix, at::Tensor L2, at::Tensor L3, at::Tensor w2,
+                                            at::Tensor w3, at::Tensor w4, double p, int64_t seed) {
+    const char* W = "lava_sentence_dgrad";
+    const SentShape s = check_lava_sentence_levels(W, L2, L3);
+    check_lava_sentence_weights(W, w2, w3, w4, L2);
+    check_lava_sentence_dpix(W, dpix, s, L2, p, seed);
+    at::Tensor t2 = w2.t().contiguous().to(at::kBFloat16), t3 = w3.t().contiguous().to(at::kBFloat16),
+               t4 = w4.t().contiguous().to(at::kBFloat16);                                           // [K][128]
+    at::Tensor ws = at::empty({s.N * (s.h3 / 2) * (s.w3 / 2), 256}, L2.options().dtype(at::kFloat));
+    at::Tensor dL2 = at::empty_like(L2), dL3 = at::empty_like(L3);
+    check_launch(rt1_lava_sentence_dgrad(dpix.data_ptr<float>(), bf16_ptr(L3), bf16_ptr(t2), bf16_ptr(t3), bf16_ptr(t4),
+                                         s.N, s.h2, s.w2, s.h3, s.w3, (float)p, (uint32_t)seed, ws.data_ptr<float>(),
+                                         bf16_ptr(dL2), bf16_ptr(dL3), cur_stream()),
+                 W);
+    return {dL2, dL3};
+}
+
+// -> (dW2, db2, dW3, db3, dW4, db4) fp32
+std::vector<at::Tensor> lava_sentence_wgrad(at::Tensor dpix, at::Tensor L2, at::Tensor L3, double p, int64_t seed) {
+    const char* W = "lava_sentence_wgrad";
+    const SentShape s = check_lava_sentence_levels(W, L2, L3);
+    check_lava_sentence_dpix(W, dpix, s, L2, p, seed);
+    int64_t P[3];
+    TORCH_CHECK(rt1_lava_sentence_wgrad_partials(s.N, s.h2, s.w2, s.h3, s.w3, P), W, ": the shape is not served");
+    const auto o = L2.options().dtype(at::kFloat);
+    at::Tensor part = at::empty({P[0] * (128 * 128 + 128) + (P[1] + P[2]) * (128 * 256 + 128)}, o);
+    at::Tensor dW2 = at::empty({128, 128}, o), dW3 = at::empty({128, 256}, o), dW4 = at::empty({128, 256}, o);
+    at::Tensor db2 = at::empty({128}, o), db3 = at::empty({128}, o), db4 = at::empty({128}, o);
+    check_launch(rt1_lava_sentence_wgrad(dpix.data_ptr<float>(), bf16_ptr(L2), bf16_ptr(L3), s.N, s.h2, s.w2, s.h3,
+                                         s.w3, (float)p, (uint32_t)seed, part.data_ptr<float>(),
+                                         dW2.data_ptr<float>(), dW3.data_ptr<float>(), dW4.data_ptr<float>(),
+                                         db2.data_ptr<float>(), db3.data_ptr<float>(), db4.data_ptr<float>(),
+                                         cur_stream()),
+                 W);
+    return {dW2, db2, dW3, db3, dW4, db4};
+}
+
+bool lava_sentence_supported(int64_t c2, int64_t c3, int64_t d) {
+    return c2 > 0 && c2 <= INT32_MAX && c3 > 0 && c3 <= INT32_MAX && d > 0 && d <= INT32_MAX &&
+           rt1_lava_sentence_supported((int)c2, (int)c3, (int)d);
+}
+
+int64_t lava_sentence_tile_rows() { return rt1_lava_sentence_tile_rows(); }
+
+// workgroup partials of the weight gradient per level (2, 3, 4); empty for an unserved shape
+std::vector<int64_t> lava_sentence_wgrad_partials(int64_t N, int64_t h2, int64_t w2, int64_t h3, int64_t w3) {
+    int64_t P[3];
+    if (!rt1_lava_sentence_wgrad_partials(N, h2, w2, h3, w3, P)) return {};
+    return {P[0], P[1], P[2]};
+}
+
 // For tools/bench_lamb.py only: ONE of the three launches of flat_lamb_dev (kernel 1 moments, 2 trust, 3 apply) on the
 // same checked arguments, so that each kernel can be timed.  Not an optimizer step: kernel 3 alone applies whatever
 // trust holds.
@@ -1990,6 +2110,16 @@ PYBIND11_MODULE(_rt1_hip, m) {
           "maxpool2(relu(conv3x3_same(x NHWC, weight) + bias)) -> (y bf16, idx uint8: 0..3 winner, 4 dead)");
     m.def("lava_conv_dgrad", &lava_conv_dgrad, "its data gradient from the pooled (dy, idx): -> dx bf16 [N, H, W, cin]");
     m.def("lava_conv_wgrad", &lava_conv_wgrad, "its weight and bias gradients from x and the pooled (dy, idx): fp32");
+    m.def("lava_sentence_supported", &lava_sentence_supported,
+          "whether the lava_sentence kernels serve level channels (c2, c3) and d_model");
+    m.def("lava_sentence_tile_rows", &lava_sentence_tile_rows, "sentence rows one workgroup owns");
+    m.def("lava_sentence_wgrad_partials", &lava_sentence_wgrad_partials,
+          "workgroup partials per level lava_sentence_wgrad writes for (N, h2, w2, h3, w3); empty when unserved");
+    m.def("lava_sentence_fwd", &lava_sentence_fwd,
+          "visual sentence of levels (2, 3, 4): drop((A W^T + b) sqrt(128) + pos) -> pixels fp32 [N, S, 128]");
+    m.def("lava_sentence_dgrad", &lava_sentence_dgrad, "its data gradients: -> (dL2, dL3) bf16, pool gradient in dL3");
+    m.def("lava_sentence_wgrad", &lava_sentence_wgrad,
+          "its parameter gradients: -> (dW2, db2, dW3, db3, dW4, db4) fp32, bitwise reproducible");
     m.def("lr_schedule_dev", &lr_schedule_dev,
           "per-step lr schedule on the device: state[1] / group_state[g][0] <- lr_base[g] * f(effective Adam step)");
     m.def("gradnorm_partials", &gradnorm_partials, "fp64 partial sums grad_sumsq writes for n floats");

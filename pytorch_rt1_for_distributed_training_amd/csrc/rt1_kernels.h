@@ -96,6 +96,30 @@ int rt1_lava_conv_wgrad(const void* x, int x_kind, const uint16_t* dy, const uin
                         int64_t W, int cin, int cout, float* part, float* dbpart, float* dW, float* db,
                         hipStream_t stream);
 
+// lavasent.hip: the LAVA visual sentence, pixels fp32 [N, S, 128] = drop((A_l W_l^T + b_l) sqrt(128) + pos) over fuse
+// levels (2, 3, 4): L2 bf16 [N, h2, w2, 128], L3 bf16 [N, h3, w3, 256], level 4 = the VALID 2x2 maxpool of L3 formed
+// while staging; S = h2 w2 + h3 w3 + (h3 / 2)(w3 / 2), h2, w2 >= 1, h3, w3 >= 2.  Dropout by counter hash on
+// (seed, n S + r, column), no mask stored.  Weights as bf16 packs (raw uint16_t): wp_l = W_l [128][K_l] for the
+// forward, wt_l = W_l^T [K_l][128] for the data gradient.
+//   fwd    one launch over the row tiles of all three levels
+//   dgrad  dpix fp32 [N, S, 128] -> dL2, dL3 bf16 (dL3 includes the pool gradient, gathered); two launches, workspace
+//          ws fp32 [N (h3 / 2)(w3 / 2), 256]
+//   wgrad  dpix, L2, L3 -> dW_l fp32 [128][K_l], db_l fp32 [128]; workspace part fp32, sum_l P_l (128 K_l + 128) with
+//          P = rt1_lava_sentence_wgrad_partials(...); partials added in a fixed order, no atomics
+int rt1_lava_sentence_supported(int c2, int c3, int d);
+int rt1_lava_sentence_tile_rows();
+int rt1_lava_sentence_wgrad_partials(int64_t N, int64_t h2, int64_t w2, int64_t h3, int64_t w3, int64_t* P);
+int rt1_lava_sentence_fwd(const uint16_t* L2, const uint16_t* L3, const uint16_t* wp2, const uint16_t* wp3,
+                          const uint16_t* wp4, const float* b2, const float* b3, const float* b4, const float* pos,
+                          int64_t N, int64_t h2, int64_t w2, int64_t h3, int64_t w3, float p, uint32_t seed, float* pix,
+                          hipStream_t stream);
+int rt1_lava_sentence_dgrad(const float* dpix, const uint16_t* L3, const uint16_t* wt2, const uint16_t* wt3,
+                            const uint16_t* wt4, int64_t N, int64_t h2, int64_t w2, int64_t h3, int64_t w3, float p,
+                            uint32_t seed, float* ws, uint16_t* dL2, uint16_t* dL3, hipStream_t stream);
+int rt1_lava_sentence_wgrad(const float* dpix, const uint16_t* L2, const uint16_t* L3, int64_t N, int64_t h2,
+                            int64_t w2, int64_t h3, int64_t w3, float p, uint32_t seed, float* part, float* dW2,
+                            float* dW3, float* dW4, float* db2, float* db3, float* db4, hipStream_t stream);
+
 // gradnorm.hip (deterministic global gradient norm -> clip_state fp32[8] = {norm, coef, ok, skipped steps, clipped
 // steps, consecutive skipped steps, 0, 0}; rt1_gradnorm_partials: workgroups / fp64 partials for n floats, a function
 // of n alone, 0 for n <= 0)

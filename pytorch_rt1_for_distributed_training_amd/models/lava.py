@@ -43,6 +43,7 @@ class LavaConfig:
     dropout: float = 0.1
     backend: str = "torch"                    # pixel-language attention: torch | hip | auto (ops/lava_attention.py)
     encoder_backend: str = "torch"            # conv-maxpool image encoder: torch | hip | auto (ops/lava_conv.py)
+    sentence_backend: str = "torch"           # level projections -> pixels: torch | hip | auto (ops/lava_sentence.py)
 
 
 def _dense(i: int, o: int) -> nn.Linear:
@@ -123,6 +124,16 @@ class ConvMaxpoolEncoder(nn.Module):
         levels.append(F.max_pool2d(x, 2))
         return levels
 
+    def stages_nhwc(self, x):              # hip only: the four stage outputs as the kernels store them, NHWC bf16
+        if self.backend != "hip":
+            raise ValueError("the NHWC bf16 stage outputs exist only on the hip encoder backend")
+        from ..ops.lava_conv import conv_relu_pool
+        stages = []
+        for conv in self.convs:
+            x = conv_relu_pool(x, conv)
+            stages.append(x)
+        return stages
+
 
 class CrossLayer(nn.Module):
     """Pre-norm language(query) -> pixels(key/value) attention with a residual on the language path."""
@@ -192,6 +203,7 @@ class SequenceLAVMSE(nn.Module):
         if cfg.backend != "torch":
             from ..ops.lava_attention import resolve_backend
             self.backend = resolve_backend(cfg.backend, d, 2)            # ValueError when hip cannot be served
+        self.sentence_backend = self._resolve_sentence(cfg)
         self.cross = nn.ModuleList(CrossLayer(d, 2, d, cfg.dropout, self.backend) for _ in range(cfg.num_layers))
         self.fuse_norm = nn.LayerNorm(d)
         self.temporal_in = _dense(d, d)
@@ -203,6 +215,33 @@ class SequenceLAVMSE(nn.Module):
         self.drop = nn.Dropout(cfg.dropout)
         self.register_buffer("pos_t", sincos_1d(cfg.sequence_length, d), persistent=False)
         self._pos2d = {}
+
+    def _resolve_sentence(self, cfg: LavaConfig) -> str:
+        """``hip`` consumes the hip encoder's NHWC bf16 outputs and serves fuse levels (2, 3, 4) at d_model 128."""
+        if cfg.sentence_backend == "torch":
+            return "torch"
+        from ..ops.lava_sentence import D_MODEL, FUSE_LAYERS, resolve_backend
+        missing = None
+        if self.image_encoder.backend != "hip":
+            missing = "the hip sentence backend needs the hip encoder backend (encoder_backend='hip')"
+        elif tuple(cfg.pyramid_fuse_layers) != FUSE_LAYERS:
+            missing = (f"the hip sentence backend serves pyramid_fuse_layers == {FUSE_LAYERS}, "
+                       f"got {tuple(cfg.pyramid_fuse_layers)}")
+        elif cfg.d_model != D_MODEL:
+            missing = f"the hip sentence backend serves d_model == {D_MODEL}, got {cfg.d_model}"
+        if missing is None:
+            return resolve_backend(cfg.sentence_backend, [self.image_encoder.channels[i] for i in FUSE_LAYERS],
+                                   cfg.d_model)
+        if cfg.sentence_backend == "auto":
+            return "torch"
+        resolve_backend(cfg.sentence_backend)                           # an unknown name or a missing GPU comes first
+        raise ValueError(missing)
+
+    def _pos_sentence(self, shapes, device) -> torch.Tensor:
+        key = (tuple(shapes), str(device))
+        if key not in self._pos2d:
+            self._pos2d[key] = torch.cat([self._pos(h, w, device) for h, w in shapes], 0).contiguous()
+        return self._pos2d[key]
 
     def _pos(self, h: int, w: int, device) -> torch.Tensor:
         key = (h, w, str(device))
@@ -220,15 +259,24 @@ class SequenceLAVMSE(nn.Module):
             if x.dtype == torch.uint8:
                 x = x.float() / 255.0
             x = x.permute(0, 3, 1, 2).contiguous()                     # NHWC -> NCHW
-        levels = self.image_encoder(x)
         d = self.cfg.d_model
-        sent = []
-        for i in self.cfg.pyramid_fuse_layers:
-            f = levels[i]                                               # (N, C, h, w)
-            h, w = f.shape[-2:]
-            v = self.visual_proj[str(i)](f.flatten(2).transpose(1, 2)) * math.sqrt(d)
-            sent.append(v + self._pos(h, w, v.device))
-        pixels = self.drop(torch.cat(sent, dim=1))                      # (N, sum hw, d)
+        if self.sentence_backend == "hip":
+            # projections, scale, positions, cat and dropout in one MFMA kernel over the NHWC bf16 stage outputs
+            # (lavasent.hip); level 4 is pooled from level 3 inside it
+            from ..ops.lava_sentence import visual_sentence
+            l2, l3 = self.image_encoder.stages_nhwc(x)[2:4]
+            (h2, w2), (h3, w3) = l2.shape[1:3], l3.shape[1:3]
+            pos = self._pos_sentence(((h2, w2), (h3, w3), (h3 // 2, w3 // 2)), l2.device)
+            pixels = visual_sentence(l2, l3, self.visual_proj, pos, self.cfg.dropout, self.training)
+        else:
+            levels = self.image_encoder(x)
+            sent = []
+            for i in self.cfg.pyramid_fuse_layers:
+                f = levels[i]                                           # (N, C, h, w)
+                h, w = f.shape[-2:]
+                v = self.visual_proj[str(i)](f.flatten(2).transpose(1, 2)) * math.sqrt(d)
+                sent.append(v + self._pos(h, w, v.device))
+            pixels = self.drop(torch.cat(sent, dim=1))                  # (N, sum hw, d)
         q = self.drop(self.lang_proj(lang.reshape(b * t, -1).to(self.lang_proj.weight.dtype)) * math.sqrt(d))[:, None]
         for layer in self.cross:
             q = layer(pixels, q)
