@@ -680,6 +680,155 @@ std::vector<int64_t> lava_sentence_wgrad_partials(int64_t N, int64_t h2, int64_t
     return {P[0], P[1], P[2]};
 }
 
+// LAVA cross-layer language rows (csrc/kernels/lavalang.hip): every tensor fp32, contiguous, 16-byte aligned, on the
+// device of the first; `rows` [N, 128] tensors share N, `shape`d ones are parameters or per-frame [N, 2, 128] vectors.
+int64_t check_lava_lang(const char* W, std::initializer_list<std::pair<const char*, const at::Tensor*>> rows,
+                        std::initializer_list<std::tuple<const char*, const at::Tensor*, std::vector<int64_t>>> shaped) {
+    const at::Tensor& first = *rows.begin()->second;
+    for (const auto& [name, t] : rows) {
+        check_dev(*t, name, at::kFloat);
+        TORCH_CHECK(t->dim() == 2 && t->size(1) == 128 && t->size(0) >= 1 && t->size(0) == first.size(0), W, ": ", name,
+                    " has shape ", t->sizes(), ", expected [", first.size(0), ", 128]");
+        TORCH_CHECK(aligned16(*t) && t->device() == first.device(), W, ": ", name, " misaligned or on another device");
+    }
+    for (const auto& [name, t, shape] : shaped) {
+        check_dev(*t, name, at::kFloat);
+        std::vector<int64_t> want = shape;
+        for (auto& s : want) s = s < 0 ? first.size(0) : s;
+        TORCH_CHECK(t->sizes() == at::IntArrayRef(want), W, ": ", name, " has shape ", t->sizes(), ", expected ", want);
+        TORCH_CHECK(aligned16(*t) && t->device() == first.device(), W, ": ", name, " misaligned or on another device");
+    }
+    TORCH_CHECK(rt1_lava_lang_partials(first.size(0)) > 0, W, ": too many rows");
+    return first.size(0);
+}
+
+void check_lava_lang_drop(const char* W, double p, int64_t seed) {
+    TORCH_CHECK(p >= 0.0 && p < 1.0, W, ": dropout p = ", p, " is not in [0, 1)");
+    TORCH_CHECK(seed >= 0 && seed <= (int64_t)UINT32_MAX, W, ": seed does not fit 32 bits");
+}
+
+// the partial workspace of a backward launch (one partial goes straight to the result)
+at::Tensor lava_lang_part(int64_t N, int64_t floats, const at::TensorOptions& o) {
+    const int64_t P = rt1_lava_lang_partials(N);
+    return at::empty({P > 1 ? P * floats : 1}, o);
+}
+
+at::Tensor lava_lang_ln_fwd(at::Tensor x, at::Tensor g, at::Tensor b, double eps) {
+    const char* W = "lava_lang_ln_fwd";
+    const int64_t N = check_lava_lang(W, {{"x", &x}}, {{"weight", &g, {128}}, {"bias", &b, {128}}});
+    at::Tensor y = at::empty_like(x);
+    check_launch(rt1_lava_lang_ln_fwd(x.data_ptr<float>(), g.data_ptr<float>(), b.data_ptr<float>(), (float)eps, N,
+                                      y.data_ptr<float>(), cur_stream()),
+                 W);
+    return y;
+}
+
+// -> (dx [N, 128], d weight [128], d bias [128])
+std::vector<at::Tensor> lava_lang_ln_bwd(at::Tensor dy, at::Tensor x, at::Tensor g, double eps) {
+    const char* W = "lava_lang_ln_bwd";
+    const int64_t N = check_lava_lang(W, {{"dy", &dy}, {"x", &x}}, {{"weight", &g, {128}}});
+    at::Tensor dx = at::empty_like(x), dgb = at::empty({2, 128}, x.options()), part = lava_lang_part(N, 256, x.options());
+    check_launch(rt1_lava_lang_ln_bwd(dy.data_ptr<float>(), x.data_ptr<float>(), g.data_ptr<float>(), (float)eps, N,
+                                      part.data_ptr<float>(), dx.data_ptr<float>(), dgb.data_ptr<float>(),
+                                      cur_stream()),
+                 W);
+    return {dx, dgb[0], dgb[1]};
+}
+
+// -> (out, ln_out or an undefined tensor, x3, f1); the epilogue LayerNorm runs when ge is given
+std::vector<at::Tensor> lava_lang_tail_fwd(at::Tensor lang, at::Tensor ctx, at::Tensor Wo, at::Tensor bo, at::Tensor gf,
+                                           at::Tensor bf, double epsf, at::Tensor W1, at::Tensor b1, at::Tensor W2,
+                                           at::Tensor b2, const OptT& ge, const OptT& be, double epse, double p,
+                                           int64_t seed) {
+    const char* W = "lava_lang_tail_fwd";
+    const int64_t N = check_lava_lang(W, {{"lang", &lang}, {"ctx", &ctx}},
+                                      {{"out_proj.weight", &Wo, {128, 128}}, {"out_proj.bias", &bo, {128}},
+                                       {"ln_ffn.weight", &gf, {128}}, {"ln_ffn.bias", &bf, {128}},
+                                       {"ff1.weight", &W1, {128, 128}}, {"ff1.bias", &b1, {128}},
+                                       {"ff2.weight", &W2, {128, 128}}, {"ff2.bias", &b2, {128}}});
+    check_lava_lang_drop(W, p, seed);
+    TORCH_CHECK(ge.has_value() == be.has_value(), W, ": the epilogue LayerNorm needs weight and bias");
+    if (ge.has_value()) check_lava_lang(W, {{"lang", &lang}}, {{"epilogue weight", &*ge, {128}}, {"epilogue bias", &*be, {128}}});
+    at::Tensor out = at::empty_like(lang), x3 = at::empty_like(lang), f1 = at::empty_like(lang), ln_out;
+    if (ge.has_value()) ln_out = at::empty_like(lang);
+    check_launch(rt1_lava_lang_tail_fwd(lang.data_ptr<float>(), ctx.data_ptr<float>(), Wo.data_ptr<float>(),
+                                        bo.data_ptr<float>(), gf.data_ptr<float>(), bf.data_ptr<float>(), (float)epsf,
+                                        W1.data_ptr<float>(), b1.data_ptr<float>(), W2.data_ptr<float>(),
+                                        b2.data_ptr<float>(), ge.has_value() ? ge->data_ptr<float>() : nullptr,
+                                        ge.has_value() ? be->data_ptr<float>() : nullptr, (float)epse, (float)p,
+                                        (uint32_t)seed, N, x3.data_ptr<float>(), f1.data_ptr<float>(),
+                                        out.data_ptr<float>(), ge.has_value() ? ln_out.data_ptr<float>() : nullptr,
+                                        cur_stream()),
+                 W);
+    return {out, ln_out, x3, f1};
+}
+
+// -> (dlang, dctx, dWo, dbo, d gf, d bf, dW1, db1, dW2, db2, d ge, d be); the last two are zeros without the epilogue
+std::vector<at::Tensor> lava_lang_tail_bwd(at::Tensor dout, const OptT& dln, at::Tensor x3, at::Tensor f1,
+                                           const OptT& out, at::Tensor ctx, at::Tensor Wo, at::Tensor gf, at::Tensor bf,
+                                           double epsf, at::Tensor W1, at::Tensor W2, const OptT& ge, double epse,
+                                           double p, int64_t seed) {
+    const char* W = "lava_lang_tail_bwd";
+    const int64_t N = check_lava_lang(W, {{"dout", &dout}, {"x3", &x3}, {"f1", &f1}, {"ctx", &ctx}},
+                                      {{"out_proj.weight", &Wo, {128, 128}}, {"ln_ffn.weight", &gf, {128}},
+                                       {"ln_ffn.bias", &bf, {128}}, {"ff1.weight", &W1, {128, 128}},
+                                       {"ff2.weight", &W2, {128, 128}}});
+    check_lava_lang_drop(W, p, seed);
+    TORCH_CHECK(dln.has_value() == out.has_value() && dln.has_value() == ge.has_value(), W,
+                ": the epilogue LayerNorm needs d ln_out, out and its weight");
+    if (dln.has_value())
+        check_lava_lang(W, {{"dout", &dout}, {"d ln_out", &*dln}, {"out", &*out}}, {{"epilogue weight", &*ge, {128}}});
+    const int64_t E = rt1_lava_lang_grad_floats();
+    const auto o = dout.options();
+    at::Tensor dlang = at::empty_like(dout), dctx = at::empty_like(dout), grads = at::empty({E}, o),
+               part = lava_lang_part(N, E, o);
+    check_launch(rt1_lava_lang_tail_bwd(dout.data_ptr<float>(), dln.has_value() ? dln->data_ptr<float>() : nullptr,
+                                        x3.data_ptr<float>(), f1.data_ptr<float>(),
+                                        out.has_value() ? out->data_ptr<float>() : nullptr, ctx.data_ptr<float>(),
+                                        Wo.data_ptr<float>(), gf.data_ptr<float>(), bf.data_ptr<float>(), (float)epsf,
+                                        W1.data_ptr<float>(), W2.data_ptr<float>(),
+                                        ge.has_value() ? ge->data_ptr<float>() : nullptr, (float)epse, (float)p,
+                                        (uint32_t)seed, N, part.data_ptr<float>(), dlang.data_ptr<float>(),
+                                        dctx.data_ptr<float>(), grads.data_ptr<float>(), cur_stream()),
+                 W);
+    const int64_t M = 128 * 128;
+    auto mat = [&](int64_t i) { return grads.narrow(0, i * M, M).view({128, 128}); };
+    auto vec = [&](int64_t i) { return grads.narrow(0, 3 * M + i * 128, 128); };
+    return {dlang, dctx, mat(0), vec(0), vec(3), vec(4), mat(1), vec(1), mat(2), vec(2), vec(5), vec(6)};
+}
+
+// the sums over frames of lava_xattn_bwd's per-frame outputs -> (d in_proj_weight [384, 128], d in_proj_bias [384],
+// d ln_pix weight [128], d ln_pix bias [128])
+std::vector<at::Tensor> lava_lang_attn_pgrad(at::Tensor Q, at::Tensor dQ, at::Tensor q, at::Tensor dctx, at::Tensor u,
+                                             at::Tensor w, at::Tensor z, at::Tensor e, at::Tensor ln_w,
+                                             at::Tensor ln_b) {
+    const char* W = "lava_lang_attn_pgrad";
+    const int64_t N = check_lava_lang(W, {{"Q", &Q}, {"dQ", &dQ}, {"q", &q}, {"dctx", &dctx}},
+                                      {{"u", &u, {-1, 2, 128}}, {"w", &w, {-1, 2, 128}}, {"z", &z, {-1, 2, 128}},
+                                       {"e", &e, {-1, 2, 128}}, {"ln_weight", &ln_w, {128}}, {"ln_bias", &ln_b, {128}}});
+    const int64_t E = rt1_lava_lang_grad_floats();
+    at::Tensor grads = at::empty({E}, Q.options()), part = lava_lang_part(N, E, Q.options());
+    check_launch(rt1_lava_lang_attn_pgrad(Q.data_ptr<float>(), dQ.data_ptr<float>(), q.data_ptr<float>(),
+                                          dctx.data_ptr<float>(), u.data_ptr<float>(), w.data_ptr<float>(),
+                                          z.data_ptr<float>(), e.data_ptr<float>(), ln_w.data_ptr<float>(),
+                                          ln_b.data_ptr<float>(), N, part.data_ptr<float>(), grads.data_ptr<float>(),
+                                          cur_stream()),
+                 W);
+    const int64_t M = 3 * 128 * 128;
+    return {grads.narrow(0, 0, M).view({384, 128}), grads.narrow(0, M, 384), grads.narrow(0, M + 384, 128),
+            grads.narrow(0, M + 512, 128)};
+}
+
+bool lava_lang_supported(int64_t d, int64_t dff, int64_t heads) {
+    return d > 0 && d <= INT32_MAX && dff > 0 && dff <= INT32_MAX && heads > 0 && heads <= INT32_MAX &&
+           rt1_lava_lang_supported((int)d, (int)dff, (int)heads);
+}
+
+int64_t lava_lang_tile_rows() { return rt1_lava_lang_tile_rows(); }
+
+// workgroup partials a backward launch over N rows writes; 0 when N cannot be served
+int64_t lava_lang_partials(int64_t N) { return rt1_lava_lang_partials(N); }
+
 // For tools/bench_lamb.py only: ONE of the three launches of flat_lamb_dev (kernel 1 moments, 2 trust, 3 apply) on the
 // same checked arguments, so that each kernel can be timed.  Not an optimizer step: kernel 3 alone applies whatever
 // trust holds.
@@ -2120,6 +2269,19 @@ PYBIND11_MODULE(_rt1_hip, m) {
     m.def("lava_sentence_dgrad", &lava_sentence_dgrad, "its data gradients: -> (dL2, dL3) bf16, pool gradient in dL3");
     m.def("lava_sentence_wgrad", &lava_sentence_wgrad,
           "its parameter gradients: -> (dW2, db2, dW3, db3, dW4, db4) fp32, bitwise reproducible");
+    m.def("lava_lang_supported", &lava_lang_supported, "whether the lava_lang kernels serve (d_model, dff, heads)");
+    m.def("lava_lang_tile_rows", &lava_lang_tile_rows, "language rows one workgroup owns");
+    m.def("lava_lang_partials", &lava_lang_partials, "workgroup partials a lava_lang backward over N rows writes");
+    m.def("lava_lang_ln_fwd", &lava_lang_ln_fwd, "row LayerNorm of x fp32 [N, 128]");
+    m.def("lava_lang_ln_bwd", &lava_lang_ln_bwd, "its backward: -> (dx, d weight, d bias), bitwise reproducible");
+    m.def("lava_lang_tail_fwd", &lava_lang_tail_fwd,
+          "CrossLayer's rows after the attention, out projection to FFN residual (+ an epilogue LayerNorm): -> (out, "
+          "ln_out, x3, f1)");
+    m.def("lava_lang_tail_bwd", &lava_lang_tail_bwd,
+          "its backward: -> (dlang, dctx, dWo, dbo, d ln_ffn w, b, dW1, db1, dW2, db2, d epilogue w, b)");
+    m.def("lava_lang_attn_pgrad", &lava_lang_attn_pgrad,
+          "parameter gradients of lava_xattn from its per-frame outputs: -> (d in_proj_weight, d in_proj_bias, d ln "
+          "weight, d ln bias)");
     m.def("lr_schedule_dev", &lr_schedule_dev,
           "per-step lr schedule on the device: state[1] / group_state[g][0] <- lr_base[g] * f(effective Adam step)");
     m.def("gradnorm_partials", &gradnorm_partials, "fp64 partial sums grad_sumsq writes for n floats");

@@ -120,6 +120,39 @@ int rt1_lava_sentence_wgrad(const float* dpix, const uint16_t* L2, const uint16_
                             int64_t w2, int64_t h3, int64_t w3, float p, uint32_t seed, float* part, float* dW2,
                             float* dW3, float* dW4, float* db2, float* db3, float* db4, hipStream_t stream);
 
+// lavalang.hip: the [N, 128] language rows of a LAVA CrossLayer around the folded attention (d_model = dff = 128, 2
+// heads), all fp32, products on the fp32 MFMA.  One workgroup per 16-row tile; parameter gradients as one partial per
+// workgroup, P = rt1_lava_lang_partials(N), added in partial order (no atomics; no reduce launch when P == 1).
+//   ln_fwd / ln_bwd   a row LayerNorm; dgb fp32 [256] = (d weight, d bias); workspace part fp32 [P][256]
+//   tail_fwd    x3 = lang + drop1(ctx Wo^T + bo), f1 = relu(LN_ffn(x3) W1^T + b1), out = x3 + drop2(f1 W2^T + b2) and,
+//               with ge != nullptr, ln_out = LN(out; ge, be, epse).  Dropout by counter hash on (seed, 2 row + site,
+//               column), no mask stored.  x3 and f1 are what the backward needs (and out, for the epilogue LayerNorm)
+//   tail_bwd    dout and (dln != nullptr) d ln_out -> dlang, dctx [N, 128] and grads fp32 [rt1_lava_lang_grad_floats()]
+//               = dWo, dW1, dW2 [128][128], then dbo, db1, db2, d gf, d bf, d ge, d be, 0 [128] each; workspace part
+//               fp32 [P][grad floats]
+//   attn_pgrad  the sums over frames of lavaxattn.hip's per-frame Q, dQ, q, dctx [N, 128], u, w, z, e [N, 2, 128]:
+//               grads = d in_proj_weight [384][128], d in_proj_bias [384] (K third exactly 0), d ln_pix weight, bias
+//               [128], 0 [3][128]; g, b: ln_pix.  Same workspace.
+int rt1_lava_lang_supported(int d, int dff, int H);
+int rt1_lava_lang_tile_rows();
+int rt1_lava_lang_partials(int64_t N);
+int rt1_lava_lang_grad_floats();
+int rt1_lava_lang_ln_fwd(const float* x, const float* g, const float* b, float eps, int64_t N, float* y,
+                         hipStream_t stream);
+int rt1_lava_lang_ln_bwd(const float* dy, const float* x, const float* g, float eps, int64_t N, float* part, float* dx,
+                         float* dgb, hipStream_t stream);
+int rt1_lava_lang_tail_fwd(const float* lang, const float* ctx, const float* Wo, const float* bo, const float* gf,
+                           const float* bf, float epsf, const float* W1, const float* b1, const float* W2,
+                           const float* b2, const float* ge, const float* be, float epse, float p, uint32_t seed,
+                           int64_t N, float* x3, float* f1, float* out, float* ln_out, hipStream_t stream);
+int rt1_lava_lang_tail_bwd(const float* dout, const float* dln, const float* x3, const float* f1, const float* out,
+                           const float* ctx, const float* Wo, const float* gf, const float* bf, float epsf,
+                           const float* W1, const float* W2, const float* ge, float epse, float p, uint32_t seed,
+                           int64_t N, float* part, float* dlang, float* dctx, float* grads, hipStream_t stream);
+int rt1_lava_lang_attn_pgrad(const float* Q, const float* dQ, const float* q, const float* dctx, const float* u,
+                             const float* w, const float* z, const float* e, const float* g, const float* b, int64_t N,
+                             float* part, float* grads, hipStream_t stream);
+
 // gradnorm.hip (deterministic global gradient norm -> clip_state fp32[8] = {norm, coef, ok, skipped steps, clipped
 // steps, consecutive skipped steps, 0, 0}; rt1_gradnorm_partials: workgroups / fp64 partials for n floats, a function
 // of n alone, 0 for n <= 0)

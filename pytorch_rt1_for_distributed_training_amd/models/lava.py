@@ -44,6 +44,7 @@ class LavaConfig:
     backend: str = "torch"                    # pixel-language attention: torch | hip | auto (ops/lava_attention.py)
     encoder_backend: str = "torch"            # conv-maxpool image encoder: torch | hip | auto (ops/lava_conv.py)
     sentence_backend: str = "torch"           # level projections -> pixels: torch | hip | auto (ops/lava_sentence.py)
+    language_backend: str = "torch"           # cross layers' language rows: torch | hip | auto (ops/lava_language.py)
 
 
 def _dense(i: int, o: int) -> nn.Linear:
@@ -138,15 +139,22 @@ class ConvMaxpoolEncoder(nn.Module):
 class CrossLayer(nn.Module):
     """Pre-norm language(query) -> pixels(key/value) attention with a residual on the language path."""
 
-    def __init__(self, d: int, heads: int, dff: int, dropout: float, backend: str = "torch"):
+    def __init__(self, d: int, heads: int, dff: int, dropout: float, backend: str = "torch",
+                 language_backend: str = "torch"):
         super().__init__()
         self.ln_pix, self.ln_lang, self.ln_ffn = nn.LayerNorm(d), nn.LayerNorm(d), nn.LayerNorm(d)
         self.attn = nn.MultiheadAttention(d, heads, batch_first=True)
         self.ff1, self.ff2 = _dense(d, dff), _dense(dff, dff)
         self.drop = nn.Dropout(dropout)
         self.backend = backend                                           # "torch" or "hip", already resolved
+        self.language_backend = language_backend                         # likewise; "hip" needs backend "hip"
 
     def forward(self, pix, lang):
+        if self.language_backend == "hip":
+            # ln_lang, then everything after the attention in one launch (lavalang.hip); a stack of layers goes
+            # through cross_stack as a whole, which also folds the next layer's ln_lang into this one's launch
+            from ..ops.lava_language import cross_stack
+            return cross_stack(pix, lang[:, 0], [self])[0][:, None]
         if self.backend == "hip":
             # pixel LayerNorm, K / V projections and the one-query attention in one pass over pix (lavaxattn.hip);
             # the out-projection, dropout and FFN are [N, d] work and stay as they are
@@ -204,7 +212,9 @@ class SequenceLAVMSE(nn.Module):
             from ..ops.lava_attention import resolve_backend
             self.backend = resolve_backend(cfg.backend, d, 2)            # ValueError when hip cannot be served
         self.sentence_backend = self._resolve_sentence(cfg)
-        self.cross = nn.ModuleList(CrossLayer(d, 2, d, cfg.dropout, self.backend) for _ in range(cfg.num_layers))
+        self.language_backend = self._resolve_language(cfg)
+        self.cross = nn.ModuleList(CrossLayer(d, 2, d, cfg.dropout, self.backend, self.language_backend)
+                                   for _ in range(cfg.num_layers))
         self.fuse_norm = nn.LayerNorm(d)
         self.temporal_in = _dense(d, d)
         self.temporal = nn.ModuleList(SelfLayer(d, cfg.num_heads, d, cfg.dropout)
@@ -236,6 +246,18 @@ class SequenceLAVMSE(nn.Module):
             return "torch"
         resolve_backend(cfg.sentence_backend)                           # an unknown name or a missing GPU comes first
         raise ValueError(missing)
+
+    def _resolve_language(self, cfg: LavaConfig) -> str:
+        """``hip`` consumes the hip attention kernels' per-frame outputs, so it needs ``backend`` resolved to hip."""
+        if cfg.language_backend == "torch":
+            return "torch"
+        from ..ops.lava_language import resolve_backend
+        if self.backend == "hip":
+            return resolve_backend(cfg.language_backend, cfg.d_model, cfg.d_model, 2)
+        if cfg.language_backend == "auto":
+            return "torch"
+        resolve_backend(cfg.language_backend, cfg.d_model, cfg.d_model, 2)   # an unknown name or a missing GPU comes first
+        raise ValueError("the hip language backend needs the hip attention backend (backend='hip')")
 
     def _pos_sentence(self, shapes, device) -> torch.Tensor:
         key = (tuple(shapes), str(device))
@@ -278,9 +300,14 @@ class SequenceLAVMSE(nn.Module):
                 sent.append(v + self._pos(h, w, v.device))
             pixels = self.drop(torch.cat(sent, dim=1))                  # (N, sum hw, d)
         q = self.drop(self.lang_proj(lang.reshape(b * t, -1).to(self.lang_proj.weight.dtype)) * math.sqrt(d))[:, None]
-        for layer in self.cross:
-            q = layer(pixels, q)
-        z = self.fuse_norm(q[:, 0]).reshape(b, t, d)
+        if self.language_backend == "hip":
+            # the whole cross stack's language rows on lavalang.hip; the last layer's launch carries fuse_norm
+            from ..ops.lava_language import cross_stack
+            z = cross_stack(pixels, q[:, 0], self.cross, self.fuse_norm)[1].reshape(b, t, d)
+        else:
+            for layer in self.cross:
+                q = layer(pixels, q)
+            z = self.fuse_norm(q[:, 0]).reshape(b, t, d)
         z = self.temporal_in(z) * math.sqrt(d) + self.pos_t[:t]
         z = self.drop(z)
         for layer in self.temporal:

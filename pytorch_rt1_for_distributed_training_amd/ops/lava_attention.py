@@ -3,7 +3,8 @@
 ``CrossLayer`` attends with ONE language query per frame to the S pixel rows of the visual sentence.  With one query
 the pixel LayerNorm, the K / V projections and the attention fold into one streamed pass over ``pixels`` (forward) and
 one read plus the ``dpix`` write (backward); see the kernel file for the algebra.  The kernels return per-frame
-vectors; the sums over frames -- the parameter gradients, [d, N] x [N, d] products -- are fp32 torch here.
+vectors; the sums over frames -- the parameter gradients, [d, N] x [N, d] products -- are fp32 torch here, or with the
+hip language backend (``lava_language.py``) one kernel of ``csrc/kernels/lavalang.hip``.
 """
 from __future__ import annotations
 
@@ -64,8 +65,23 @@ class LavaCrossAttnFn(torch.autograd.Function):
         return dpix, dq, d_ln_w, d_ln_b, None, d_in_w, d_in_b
 
 
-def cross_attention(pixels, q, ln_pix, attn):
+class LavaCrossAttnHipSumsFn(LavaCrossAttnFn):
+    """The same op; its backward leaves the sums over frames to ``lava_language.attn_param_grads``."""
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dctx):
+        from .lava_language import attn_param_grads
+        pixels, q, ln_w, ln_b, in_w, in_b, z, lse, Q = ctx.saved_tensors
+        dctx = dctx.contiguous()
+        dpix, dq, dQ, u, w, e = load().lava_xattn_bwd(dctx, pixels, Q, z, lse, ln_w, ln_b, ctx.eps, in_w, in_b)
+        d_in_w, d_in_b, d_ln_w, d_ln_b = attn_param_grads(Q, dQ, q, dctx, u, w, z, e, ln_w, ln_b)
+        return dpix, dq, d_ln_w, d_ln_b, None, d_in_w, d_in_b
+
+
+def cross_attention(pixels, q, ln_pix, attn, hip_sums=False):
     """The op on a ``CrossLayer``'s own modules: ``ln_pix`` an ``nn.LayerNorm``, ``attn`` an
-    ``nn.MultiheadAttention``; q [N, d] is ``ln_lang(lang)``."""
-    return LavaCrossAttnFn.apply(pixels, q, ln_pix.weight, ln_pix.bias, ln_pix.eps, attn.in_proj_weight,
-                                 attn.in_proj_bias)
+    ``nn.MultiheadAttention``; q [N, d] is ``ln_lang(lang)``.  ``hip_sums``: the parameter gradients' sums over frames
+    on the HIP language kernels instead of torch."""
+    fn = LavaCrossAttnHipSumsFn if hip_sums else LavaCrossAttnFn
+    return fn.apply(pixels, q, ln_pix.weight, ln_pix.bias, ln_pix.eps, attn.in_proj_weight, attn.in_proj_bias)

@@ -50,6 +50,9 @@ def main(argv=None):
     ap.add_argument("--sentence_backend", choices=["torch", "hip", "auto"], default="torch",
                     help="level projections into the visual sentence: eager torch, the fused MFMA HIP kernels (needs "
                          "--encoder_backend hip), or hip when available")
+    ap.add_argument("--language_backend", choices=["torch", "hip", "auto"], default="torch",
+                    help="the cross layers' language rows (LayerNorms, out projection, FFN): eager torch, the fused fp32 "
+                         "MFMA HIP kernels (needs --backend hip), or hip when available")
     ap.add_argument("--freeze_keys", nargs="*", default=[], help="parameter-name substrings to keep frozen")
     ap.add_argument("--pretrained", nargs="*", default=[],
                     help="PATH:CKPT_PREFIX=MODEL_PREFIX[,CKPT_PREFIX=MODEL_PREFIX] pretrained checkpoints")
@@ -78,7 +81,8 @@ def main(argv=None):
         stats = normalization.compute_dataset_statistics(sim_demos.action_batches(ds), num_samples=len(ds))
     stats = normalization.broadcast_stats(stats)
     cfg = LavaConfig(sequence_length=a.sequence_length, d_model=a.d_model, backend=a.backend,
-                     encoder_backend=a.encoder_backend, sentence_backend=a.sentence_backend)
+                     encoder_backend=a.encoder_backend, sentence_backend=a.sentence_backend,
+                     language_backend=a.language_backend)
     augment = None
     if a.augment:
         from pytorch_rt1_for_distributed_training_amd.data.augment import BCAugment
