@@ -829,6 +829,101 @@ int64_t lava_lang_tile_rows() { return rt1_lava_lang_tile_rows(); }
 // workgroup partials a backward launch over N rows writes; 0 when N cannot be served
 int64_t lava_lang_partials(int64_t N) { return rt1_lava_lang_partials(N); }
 
+// LAVA policy head (csrc/kernels/lavahead.hip): every tensor fp32, contiguous, 16-byte aligned, on the device of the
+// first.  `mats` are (name, tensor, rows, columns); rows or columns < 0 are taken as they come.
+void check_lava_head(const char* W, std::initializer_list<std::tuple<const char*, const at::Tensor*, int64_t, int64_t>> mats) {
+    const at::Tensor& first = *std::get<1>(*mats.begin());
+    for (const auto& [name, t, rows, cols] : mats) {
+        check_dev(*t, name, at::kFloat);
+        TORCH_CHECK(t->dim() == 2 && (rows < 0 || t->size(0) == rows) && (cols < 0 || t->size(1) == cols), W, ": ", name,
+                    " has shape ", t->sizes(), ", expected [", rows, ", ", cols, "]");
+        TORCH_CHECK(aligned16(*t) && t->device() == first.device(), W, ": ", name, " misaligned or on another device");
+    }
+}
+
+void check_lava_head_vec(const char* W, const char* name, const at::Tensor& t, int64_t n, const at::Tensor& first) {
+    check_dev(t, name, at::kFloat);
+    TORCH_CHECK(t.dim() == 1 && t.size(0) == n, W, ": ", name, " has shape ", t.sizes(), ", expected [", n, "]");
+    TORCH_CHECK(aligned16(t) && t.device() == first.device(), W, ": ", name, " misaligned or on another device");
+}
+
+// rows 1 .. 2^20, K and N multiples of 64 up to 8192 (N < 0: the projection, whose N is the action size 1 .. 8)
+void check_lava_head_dims(const char* W, int64_t B, int64_t K, int64_t N) {
+    TORCH_CHECK(B >= 1 && B <= (1 << 20), W, ": ", B, " rows, served: 1 .. 2^20");
+    TORCH_CHECK(K >= 64 && K <= 8192 && K % 64 == 0, W, ": ", K, " input columns, served: multiples of 64 up to 8192");
+    TORCH_CHECK(N < 0 || (N >= 64 && N <= 8192 && N % 64 == 0), W, ": ", N,
+                " output columns, served: multiples of 64 up to 8192");
+}
+
+// y = pro(x) w^T + b (+ res); pro = ReLU when relu_in
+at::Tensor lava_head_linear_fwd(at::Tensor x, at::Tensor w, at::Tensor b, const OptT& res, bool relu_in) {
+    const char* W = "lava_head_linear_fwd";
+    check_lava_head(W, {{"x", &x, -1, -1}, {"weight", &w, -1, x.dim() == 2 ? x.size(1) : -1}});
+    const int64_t B = x.size(0), K = x.size(1), N = w.size(0);
+    check_lava_head_dims(W, B, K, N);
+    check_lava_head_vec(W, "bias", b, N, x);
+    if (res.has_value()) check_lava_head(W, {{"x", &x, -1, -1}, {"res", &*res, B, N}});
+    at::Tensor y = at::empty({B, N}, x.options());
+    check_launch(rt1_lava_head_linear_fwd(x.data_ptr<float>(), w.data_ptr<float>(), b.data_ptr<float>(),
+                                          res.has_value() ? res->data_ptr<float>() : nullptr, B, K, N, relu_in ? 1 : 0,
+                                          y.data_ptr<float>(), cur_stream()),
+                 W);
+    return y;
+}
+
+// -> (dx, dw, db); dx = (dy w) * relu'(x) (+ rg, the gradient a residual branch brings to x)
+std::vector<at::Tensor> lava_head_linear_bwd(at::Tensor dy, at::Tensor x, at::Tensor w, const OptT& rg, bool relu_in) {
+    const char* W = "lava_head_linear_bwd";
+    check_lava_head(W, {{"x", &x, -1, -1}, {"weight", &w, -1, x.dim() == 2 ? x.size(1) : -1}});
+    const int64_t B = x.size(0), K = x.size(1), N = w.size(0);
+    check_lava_head_dims(W, B, K, N);
+    check_lava_head(W, {{"x", &x, -1, -1}, {"dy", &dy, B, N}});
+    if (rg.has_value()) check_lava_head(W, {{"x", &x, -1, -1}, {"residual gradient", &*rg, B, K}});
+    at::Tensor dx = at::empty_like(x), dw = at::empty_like(w), db = at::empty({N}, x.options());
+    check_launch(rt1_lava_head_linear_bwd(dy.data_ptr<float>(), x.data_ptr<float>(), w.data_ptr<float>(),
+                                          rg.has_value() ? rg->data_ptr<float>() : nullptr, B, K, N, relu_in ? 1 : 0,
+                                          dx.data_ptr<float>(), dw.data_ptr<float>(), db.data_ptr<float>(),
+                                          cur_stream()),
+                 W);
+    return {dx, dw, db};
+}
+
+at::Tensor lava_head_proj_fwd(at::Tensor x, at::Tensor w, at::Tensor b) {
+    const char* W = "lava_head_proj_fwd";
+    check_lava_head(W, {{"x", &x, -1, -1}, {"weight", &w, -1, x.dim() == 2 ? x.size(1) : -1}});
+    const int64_t B = x.size(0), K = x.size(1), A = w.size(0);
+    check_lava_head_dims(W, B, K, -1);
+    TORCH_CHECK(A >= 1 && A <= 8, W, ": action size ", A, ", served: 1 .. 8");
+    check_lava_head_vec(W, "bias", b, A, x);
+    at::Tensor y = at::empty({B, A}, x.options());
+    check_launch(rt1_lava_head_proj_fwd(x.data_ptr<float>(), w.data_ptr<float>(), b.data_ptr<float>(), B, K, A,
+                                        y.data_ptr<float>(), cur_stream()),
+                 W);
+    return y;
+}
+
+// -> (dx, dw, db)
+std::vector<at::Tensor> lava_head_proj_bwd(at::Tensor dy, at::Tensor x, at::Tensor w) {
+    const char* W = "lava_head_proj_bwd";
+    check_lava_head(W, {{"x", &x, -1, -1}, {"weight", &w, -1, x.dim() == 2 ? x.size(1) : -1}});
+    const int64_t B = x.size(0), K = x.size(1), A = w.size(0);
+    check_lava_head_dims(W, B, K, -1);
+    TORCH_CHECK(A >= 1 && A <= 8, W, ": action size ", A, ", served: 1 .. 8");
+    check_lava_head(W, {{"x", &x, -1, -1}, {"dy", &dy, B, A}});
+    at::Tensor dx = at::empty_like(x), dw = at::empty_like(w), db = at::empty({A}, x.options());
+    check_launch(rt1_lava_head_proj_bwd(dy.data_ptr<float>(), x.data_ptr<float>(), w.data_ptr<float>(), B, K, A,
+                                        dx.data_ptr<float>(), dw.data_ptr<float>(), db.data_ptr<float>(), cur_stream()),
+                 W);
+    return {dx, dw, db};
+}
+
+bool lava_head_supported(int64_t din, int64_t width, int64_t action_size) {
+    return din > 0 && din <= INT32_MAX && width > 0 && width <= INT32_MAX && action_size > 0 &&
+           action_size <= INT32_MAX && rt1_lava_head_supported((int)din, (int)width, (int)action_size);
+}
+
+int64_t lava_head_row_chunk() { return rt1_lava_head_row_chunk(); }
+
 // For tools/bench_lamb.py only: ONE of the three launches of flat_lamb_dev (kernel 1 moments, 2 trust, 3 apply) on the
 // same checked arguments, so that each kernel can be timed.  Not an optimizer step: kernel 3 alone applies whatever
 // trust holds.
@@ -2282,6 +2377,13 @@ PYBIND11_MODULE(_rt1_hip, m) {
     m.def("lava_lang_attn_pgrad", &lava_lang_attn_pgrad,
           "parameter gradients of lava_xattn from its per-frame outputs: -> (d in_proj_weight, d in_proj_bias, d ln "
           "weight, d ln bias)");
+    m.def("lava_head_supported", &lava_head_supported, "whether the lava_head kernels serve (din, width, action_size)");
+    m.def("lava_head_row_chunk", &lava_head_row_chunk, "rows of the largest row chunk a lava_head workgroup owns");
+    m.def("lava_head_linear_fwd", &lava_head_linear_fwd, "y = pro(x) w^T + b (+ res), pro = ReLU when relu_in");
+    m.def("lava_head_linear_bwd", &lava_head_linear_bwd,
+          "its backward in one launch: -> (dx (+ the residual branch's gradient), dw, db), bitwise reproducible");
+    m.def("lava_head_proj_fwd", &lava_head_proj_fwd, "the action projection: x w^T + b for at most 8 output columns");
+    m.def("lava_head_proj_bwd", &lava_head_proj_bwd, "its backward in one launch: -> (dx, dw, db)");
     m.def("lr_schedule_dev", &lr_schedule_dev,
           "per-step lr schedule on the device: state[1] / group_state[g][0] <- lr_base[g] * f(effective Adam step)");
     m.def("gradnorm_partials", &gradnorm_partials, "fp64 partial sums grad_sumsq writes for n floats");

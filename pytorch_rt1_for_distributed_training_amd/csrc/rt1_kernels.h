@@ -153,6 +153,24 @@ int rt1_lava_lang_attn_pgrad(const float* Q, const float* dQ, const float* q, co
                              const float* w, const float* z, const float* e, const float* g, const float* b, int64_t N,
                              float* part, float* grads, hipStream_t stream);
 
+// lavahead.hip: the LAVA policy head (DenseResnet + action_projection), short-wide fp32 linears on [B, .] rows,
+// products on the fp32 MFMA, output columns split over the workgroups.  1 <= B <= 2^20; K, N multiples of 64 up to 8192;
+// every pointer 16-byte aligned.  No workspace, no atomics, bitwise reproducible.
+//   linear_fwd  y = pro(x) w^T + b (+ res): x [B, K], w [N, K], b [N], res [B, N] or nullptr; pro = ReLU when relu_in
+//   linear_bwd  dy [B, N], the x the forward read -> dx [B, K] = (dy w) * (relu_in ? x > 0 : 1) (+ rg [B, K] or nullptr),
+//               dw [N, K] = dy^T pro(x), db [N]; one launch
+//   proj_fwd / proj_bwd   the same without pro for N = A <= 8 columns (row dot products): y [B, A]; dx, dw [A, K], db [A]
+int rt1_lava_head_supported(int din, int width, int action_size);
+int rt1_lava_head_row_chunk();
+int rt1_lava_head_linear_fwd(const float* x, const float* w, const float* b, const float* res, int64_t B, int64_t K,
+                             int64_t N, int relu_in, float* y, hipStream_t stream);
+int rt1_lava_head_linear_bwd(const float* dy, const float* x, const float* w, const float* rg, int64_t B, int64_t K,
+                             int64_t N, int relu_in, float* dx, float* dw, float* db, hipStream_t stream);
+int rt1_lava_head_proj_fwd(const float* x, const float* w, const float* b, int64_t B, int64_t K, int64_t A, float* y,
+                           hipStream_t stream);
+int rt1_lava_head_proj_bwd(const float* dy, const float* x, const float* w, int64_t B, int64_t K, int64_t A, float* dx,
+                           float* dw, float* db, hipStream_t stream);
+
 // gradnorm.hip (deterministic global gradient norm -> clip_state fp32[8] = {norm, coef, ok, skipped steps, clipped
 // steps, consecutive skipped steps, 0, 0}; rt1_gradnorm_partials: workgroups / fp64 partials for n floats, a function
 // of n alone, 0 for n <= 0)

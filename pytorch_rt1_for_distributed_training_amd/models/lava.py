@@ -45,6 +45,7 @@ class LavaConfig:
     encoder_backend: str = "torch"            # conv-maxpool image encoder: torch | hip | auto (ops/lava_conv.py)
     sentence_backend: str = "torch"           # level projections -> pixels: torch | hip | auto (ops/lava_sentence.py)
     language_backend: str = "torch"           # cross layers' language rows: torch | hip | auto (ops/lava_language.py)
+    head_backend: str = "torch"               # dense resnet + action projection: torch | hip | auto (ops/lava_head.py)
 
 
 def _dense(i: int, o: int) -> nn.Linear:
@@ -184,16 +185,38 @@ class SelfLayer(nn.Module):
 class DenseResnet(nn.Module):
     def __init__(self, din: int, width: int, blocks: int):
         super().__init__()
+        self.backend = "torch"                                           # "hip": set, resolved, by the model that owns
+                                                                         # this and the projection (_resolve_head)
         self.inp = _dense(din, width)
         self.blocks = nn.ModuleList(nn.Sequential(nn.ReLU(), _dense(width, width // 4), nn.ReLU(),
                                                   _dense(width // 4, width // 4), nn.ReLU(),
                                                   _dense(width // 4, width)) for _ in range(blocks))
 
     def forward(self, x):
+        if self.backend == "hip":
+            # one launch per linear each way, ReLUs and the residual in their prologues and epilogues (lavahead.hip)
+            from ..ops.lava_head import dense_resnet
+            return dense_resnet(x, self)
         x = self.inp(x)
         for b in self.blocks:
             x = x + b(x)
         return x
+
+
+def _resolve_head(backend: str, head: DenseResnet, action_projection: nn.Linear) -> str:
+    """``torch | hip | auto`` -> ``torch | hip`` for a dense resnet and its action projection."""
+    if backend == "torch":
+        return "torch"
+    from ..ops.lava_head import resolve_backend                          # ValueError when hip cannot be served
+    return resolve_backend(backend, head.inp.in_features, head.inp.out_features, action_projection.out_features)
+
+
+def policy_head(x, head: DenseResnet, action_projection: nn.Linear):
+    """``action_projection(head(x))``; on hip the projection is the head's last kernel (lavahead.hip)."""
+    if head.backend == "hip":
+        from ..ops.lava_head import dense_resnet_head
+        return dense_resnet_head(x, head, action_projection)
+    return action_projection(head(x))
 
 
 class SequenceLAVMSE(nn.Module):
@@ -222,6 +245,7 @@ class SequenceLAVMSE(nn.Module):
         self.temporal_norm = nn.LayerNorm(d)
         self.head = DenseResnet(d, cfg.dense_resnet_width, cfg.dense_resnet_blocks)
         self.action_projection = _dense(cfg.dense_resnet_width, cfg.action_size)
+        self.head.backend = _resolve_head(cfg.head_backend, self.head, self.action_projection)
         self.drop = nn.Dropout(cfg.dropout)
         self.register_buffer("pos_t", sincos_1d(cfg.sequence_length, d), persistent=False)
         self._pos2d = {}
@@ -315,7 +339,7 @@ class SequenceLAVMSE(nn.Module):
         return self.temporal_norm(z.mean(dim=1))
 
     def forward(self, obs) -> torch.Tensor:
-        return self.action_projection(self.head(self.encode(obs["rgb"], obs["instruction_embedding"])))
+        return policy_head(self.encode(obs["rgb"], obs["instruction_embedding"]), self.head, self.action_projection)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -370,11 +394,12 @@ class PixelLangMSE(nn.Module):
     the encoder, then the dense resnet and an N(0, 0.05)-initialised action projection (``pixel.py:84-111``)."""
 
     def __init__(self, action_size: int = 2, dense_resnet_width: int = 1024, dense_resnet_num_blocks: int = 2,
-                 sequence_length: int = 4, lang_dim: int = 512):
+                 sequence_length: int = 4, lang_dim: int = 512, head_backend: str = "torch"):
         super().__init__()
         self.encoder = ConvMaxpoolLanguageEncoder(3 * sequence_length, lang_dim)
         self.dense_resnet = DenseResnet(256, dense_resnet_width, dense_resnet_num_blocks)
         self.action_projection = _dense(dense_resnet_width, action_size)
+        self.dense_resnet.backend = _resolve_head(head_backend, self.dense_resnet, self.action_projection)
 
     def forward(self, obs) -> torch.Tensor:
         rgb = obs["rgb"]
@@ -383,5 +408,6 @@ class PixelLangMSE(nn.Module):
         b, n, w, h, c = rgb.shape
         rgb = rgb.contiguous().reshape(b, w, h, c * n)                  # reference's channel stacking
         lang = obs.get("clip_embedding", obs.get("instruction_embedding"))[:, -1]
-        x = self.encoder(rgb.permute(0, 3, 1, 2), lang.float())
-        return self.action_projection(self.dense_resnet(x))
+        dtype = next(self.encoder.parameters()).dtype                    # fp32; fp64 in a .double() copy
+        x = self.encoder(rgb.permute(0, 3, 1, 2), lang.to(dtype))
+        return policy_head(x, self.dense_resnet, self.action_projection)

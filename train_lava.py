@@ -53,6 +53,9 @@ def main(argv=None):
     ap.add_argument("--language_backend", choices=["torch", "hip", "auto"], default="torch",
                     help="the cross layers' language rows (LayerNorms, out projection, FFN): eager torch, the fused fp32 "
                          "MFMA HIP kernels (needs --backend hip), or hip when available")
+    ap.add_argument("--head_backend", choices=["torch", "hip", "auto"], default="torch",
+                    help="the policy head (dense resnet + action projection): eager torch, the column-split fp32 MFMA "
+                         "HIP kernels, or hip when available")
     ap.add_argument("--freeze_keys", nargs="*", default=[], help="parameter-name substrings to keep frozen")
     ap.add_argument("--pretrained", nargs="*", default=[],
                     help="PATH:CKPT_PREFIX=MODEL_PREFIX[,CKPT_PREFIX=MODEL_PREFIX] pretrained checkpoints")
@@ -82,14 +85,14 @@ def main(argv=None):
     stats = normalization.broadcast_stats(stats)
     cfg = LavaConfig(sequence_length=a.sequence_length, d_model=a.d_model, backend=a.backend,
                      encoder_backend=a.encoder_backend, sentence_backend=a.sentence_backend,
-                     language_backend=a.language_backend)
+                     language_backend=a.language_backend, head_backend=a.head_backend)
     augment = None
     if a.augment:
         from pytorch_rt1_for_distributed_training_amd.data.augment import BCAugment
         augment = BCAugment(seed=a.seed + ctx.rank)
     if a.network == "pixel":
         from pytorch_rt1_for_distributed_training_amd.models.lava import PixelLangMSE
-        net = PixelLangMSE(sequence_length=a.sequence_length)
+        net = PixelLangMSE(sequence_length=a.sequence_length, head_backend=a.head_backend)
     else:
         net = SequenceLAVMSE(cfg)
     pre = []
