@@ -452,7 +452,7 @@ bool lava_xattn_supported(int64_t d, int64_t heads) {
 }
 
 // LAVA image-encoder stage conv3x3 + ReLU + maxpool2 (csrc/kernels/lavaconv.hip).  x is NHWC: bf16 activations, or
-// for the first stage the frames, uint8 or fp32 [N, H, W, 3].  weight / bias are the nn.Conv2d parameters (fp32
+// for the first stage the frames, uint8 or fp32 [N, H, W, 3 s] (s = 1 .. 4 frames stacked channel-wise).  weight / bias are the nn.Conv2d parameters (fp32
 // [cout, cin, 3, 3] / [cout]); the KB-sized bf16 packs the kernels read are formed here.
 uint16_t* bf16_ptr(const at::Tensor& t) { return reinterpret_cast<uint16_t*>(t.data_ptr()); }
 
@@ -460,7 +460,7 @@ int lava_conv_x_kind(const char* W, const at::Tensor& x, int64_t cin) {
     TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 4 && x.size(3) == cin, W,
                 ": x must be a contiguous GPU tensor [N, H, W, ", cin, "]");
     TORCH_CHECK(x.size(0) >= 1 && x.size(1) >= 2 && x.size(2) >= 2, W, ": x needs N >= 1 and H, W >= 2");
-    if (cin == 3) {                       // read value by value: no alignment asked of the frames
+    if (cin < 32) {                       // read value by value: no alignment asked of the frames
         TORCH_CHECK(x.scalar_type() == at::kByte || x.scalar_type() == at::kFloat, W,
                     ": the frames must be uint8 or float32, got ", x.scalar_type());
         return x.scalar_type() == at::kByte ? 1 : 2;
@@ -476,7 +476,7 @@ void check_lava_conv_weight(const char* W, const at::Tensor& weight, const at::T
     TORCH_CHECK(weight.size(0) <= INT32_MAX && weight.size(1) <= INT32_MAX &&
                     rt1_lava_conv_supported((int)weight.size(1), (int)weight.size(0)),
                 W, ": (cin, cout) = (", weight.size(1), ", ", weight.size(0),
-                ") is not served ((3, 32), (32, 64), (64, 128), (128, 256))");
+                ") is not served ((3 | 6 | 9 | 12, 32), (32, 64), (64, 128), (128, 256))");
     TORCH_CHECK(weight.device() == dev_of.device(), W, ": tensors on different devices");
 }
 
@@ -492,44 +492,75 @@ void check_lava_conv_pooled(const char* W, const at::Tensor& dy, const at::Tenso
                 ": dy / idx misaligned or on different devices");
 }
 
+// the language gate of a gated stage (cin >= 32): fp32 [N, cout]
+const float* lava_conv_gate(const char* W, const at::Tensor* gate, const at::Tensor& dev_of, int64_t N, int64_t cin,
+                            int64_t cout) {
+    if (gate == nullptr) return nullptr;
+    check_dev(*gate, "gate", at::kFloat);
+    TORCH_CHECK(cin >= 32, W, ": the first stage has no gated form");
+    TORCH_CHECK(gate->dim() == 2 && gate->size(0) == N && gate->size(1) == cout, W, ": gate has shape ",
+                gate->sizes(), ", expected [", N, ", ", cout, "]");
+    TORCH_CHECK(aligned16(*gate) && gate->device() == dev_of.device(), W, ": gate misaligned or on another device");
+    return gate->data_ptr<float>();
+}
+
 // -> (y bf16, idx uint8) [N, H / 2, W / 2, cout]
-std::vector<at::Tensor> lava_conv_fwd(at::Tensor x, at::Tensor weight, at::Tensor bias) {
-    const char* W = "lava_conv_fwd";
+std::vector<at::Tensor> lava_conv_fwd_impl(const char* W, at::Tensor x, at::Tensor weight, at::Tensor bias,
+                                           const at::Tensor* gate) {
     check_lava_conv_weight(W, weight, x);
     const int64_t cout = weight.size(0), cin = weight.size(1);
     const int kind = lava_conv_x_kind(W, x, cin);
+    const float* gp = lava_conv_gate(W, gate, x, x.size(0), cin, cout);
     check_dev(bias, "bias", at::kFloat);
     TORCH_CHECK(bias.numel() == cout && bias.device() == x.device(), W, ": bias must be [cout] on x's device");
     const int64_t N = x.size(0), H = x.size(1), Wd = x.size(2);
     at::Tensor wp = weight.permute({2, 3, 1, 0}).contiguous().to(at::kBFloat16);            // [9][cin][cout]
     at::Tensor y = at::empty({N, H / 2, Wd / 2, cout}, x.options().dtype(at::kBFloat16));
     at::Tensor idx = at::empty({N, H / 2, Wd / 2, cout}, x.options().dtype(at::kByte));
-    check_launch(rt1_lava_conv_fwd(x.data_ptr(), kind, bf16_ptr(wp), bias.data_ptr<float>(), N, H, Wd, (int)cin,
-                                   (int)cout, bf16_ptr(y), idx.data_ptr<uint8_t>(), cur_stream()),
+    check_launch(gp ? rt1_lava_conv_gated_fwd(bf16_ptr(x), bf16_ptr(wp), bias.data_ptr<float>(), gp, N, H, Wd,
+                                              (int)cin, (int)cout, bf16_ptr(y), idx.data_ptr<uint8_t>(), cur_stream())
+                    : rt1_lava_conv_fwd(x.data_ptr(), kind, bf16_ptr(wp), bias.data_ptr<float>(), N, H, Wd, (int)cin,
+                                        (int)cout, bf16_ptr(y), idx.data_ptr<uint8_t>(), cur_stream()),
                  W);
     return {y, idx};
 }
+std::vector<at::Tensor> lava_conv_fwd(at::Tensor x, at::Tensor weight, at::Tensor bias) {
+    return lava_conv_fwd_impl("lava_conv_fwd", x, weight, bias, nullptr);
+}
+std::vector<at::Tensor> lava_conv_gated_fwd(at::Tensor x, at::Tensor weight, at::Tensor bias, at::Tensor gate) {
+    return lava_conv_fwd_impl("lava_conv_gated_fwd", x, weight, bias, &gate);
+}
 
 // -> dx bf16 [N, H, W, cin]; (H, W) is the stage's input grid (the pooled grid does not tell an odd side)
-at::Tensor lava_conv_dgrad(at::Tensor dy, at::Tensor idx, at::Tensor weight, int64_t H, int64_t Wd) {
-    const char* W = "lava_conv_dgrad";
+at::Tensor lava_conv_dgrad_impl(const char* W, at::Tensor dy, at::Tensor idx, at::Tensor weight, int64_t H,
+                                int64_t Wd, const at::Tensor* gate) {
     check_lava_conv_weight(W, weight, dy);
     const int64_t cout = weight.size(0), cin = weight.size(1);
-    TORCH_CHECK(cin != 3, W, ": the frames have no gradient");
+    TORCH_CHECK(cin >= 32, W, ": the frames have no gradient");
     TORCH_CHECK(dy.dim() == 4 && H >= 2 && Wd >= 2, W, ": dy must be [N, H / 2, W / 2, cout]");
     const int64_t N = dy.size(0);
     check_lava_conv_pooled(W, dy, idx, N, H, Wd, cout);
+    const float* gp = lava_conv_gate(W, gate, dy, N, cin, cout);
     at::Tensor wd = weight.flip({2, 3}).permute({2, 3, 0, 1}).contiguous().to(at::kBFloat16);   // [9][cout][cin]
     at::Tensor dx = at::empty({N, H, Wd, cin}, dy.options());
-    check_launch(rt1_lava_conv_dgrad(bf16_ptr(dy), idx.data_ptr<uint8_t>(), bf16_ptr(wd), N, H, Wd, (int)cin,
-                                     (int)cout, bf16_ptr(dx), cur_stream()),
+    check_launch(gp ? rt1_lava_conv_gated_dgrad(bf16_ptr(dy), idx.data_ptr<uint8_t>(), bf16_ptr(wd), gp, N, H, Wd,
+                                                (int)cin, (int)cout, bf16_ptr(dx), cur_stream())
+                    : rt1_lava_conv_dgrad(bf16_ptr(dy), idx.data_ptr<uint8_t>(), bf16_ptr(wd), N, H, Wd, (int)cin,
+                                          (int)cout, bf16_ptr(dx), cur_stream()),
                  W);
     return dx;
 }
+at::Tensor lava_conv_dgrad(at::Tensor dy, at::Tensor idx, at::Tensor weight, int64_t H, int64_t Wd) {
+    return lava_conv_dgrad_impl("lava_conv_dgrad", dy, idx, weight, H, Wd, nullptr);
+}
+at::Tensor lava_conv_gated_dgrad(at::Tensor dy, at::Tensor idx, at::Tensor weight, at::Tensor gate, int64_t H,
+                                 int64_t Wd) {
+    return lava_conv_dgrad_impl("lava_conv_gated_dgrad", dy, idx, weight, H, Wd, &gate);
+}
 
 // -> (dW fp32 [cout, cin, 3, 3], db fp32 [cout])
-std::vector<at::Tensor> lava_conv_wgrad(at::Tensor x, at::Tensor dy, at::Tensor idx) {
-    const char* W = "lava_conv_wgrad";
+std::vector<at::Tensor> lava_conv_wgrad_impl(const char* W, at::Tensor x, at::Tensor dy, at::Tensor idx,
+                                             const at::Tensor* gate) {
     TORCH_CHECK(x.dim() == 4 && dy.dim() == 4, W, ": x must be [N, H, W, cin] and dy [N, H / 2, W / 2, cout]");
     const int64_t cin = x.size(3), cout = dy.size(3);
     TORCH_CHECK(cin <= INT32_MAX && cout <= INT32_MAX && rt1_lava_conv_supported((int)cin, (int)cout), W,
@@ -538,16 +569,115 @@ std::vector<at::Tensor> lava_conv_wgrad(at::Tensor x, at::Tensor dy, at::Tensor 
     const int64_t N = x.size(0), H = x.size(1), Wd = x.size(2);
     check_lava_conv_pooled(W, dy, idx, N, H, Wd, cout);
     TORCH_CHECK(dy.device() == x.device(), W, ": tensors on different devices");
+    const float* gp = lava_conv_gate(W, gate, x, N, cin, cout);
     const int64_t P = rt1_lava_conv_wgrad_partials(N, H, Wd, (int)cin, (int)cout);
     TORCH_CHECK(P >= 1, W, ": the shape is not served");
     const auto o = x.options().dtype(at::kFloat);
     at::Tensor part = at::empty({P, 9 * cin, cout}, o), dbpart = at::empty({P, cout}, o);
     at::Tensor dW = at::empty({cout, cin, 3, 3}, o), db = at::empty({cout}, o);
-    check_launch(rt1_lava_conv_wgrad(x.data_ptr(), kind, bf16_ptr(dy), idx.data_ptr<uint8_t>(), N, H, Wd, (int)cin,
-                                     (int)cout, part.data_ptr<float>(), dbpart.data_ptr<float>(),
-                                     dW.data_ptr<float>(), db.data_ptr<float>(), cur_stream()),
+    check_launch(gp ? rt1_lava_conv_gated_wgrad(bf16_ptr(x), bf16_ptr(dy), idx.data_ptr<uint8_t>(), gp, N, H, Wd,
+                                                (int)cin, (int)cout, part.data_ptr<float>(), dbpart.data_ptr<float>(),
+                                                dW.data_ptr<float>(), db.data_ptr<float>(), cur_stream())
+                    : rt1_lava_conv_wgrad(x.data_ptr(), kind, bf16_ptr(dy), idx.data_ptr<uint8_t>(), N, H, Wd,
+                                          (int)cin, (int)cout, part.data_ptr<float>(), dbpart.data_ptr<float>(),
+                                          dW.data_ptr<float>(), db.data_ptr<float>(), cur_stream()),
                  W);
     return {dW, db};
+}
+std::vector<at::Tensor> lava_conv_wgrad(at::Tensor x, at::Tensor dy, at::Tensor idx) {
+    return lava_conv_wgrad_impl("lava_conv_wgrad", x, dy, idx, nullptr);
+}
+std::vector<at::Tensor> lava_conv_gated_wgrad(at::Tensor x, at::Tensor dy, at::Tensor idx, at::Tensor gate) {
+    return lava_conv_wgrad_impl("lava_conv_gated_wgrad", x, dy, idx, &gate);
+}
+
+// -> dgate fp32 [N, cout] of a gated stage from the pooled dy and the stage's own output y (same shape, bf16);
+// (H, W) is the stage's input grid
+at::Tensor lava_conv_dgate(at::Tensor dy, at::Tensor y, at::Tensor gate, int64_t cin, int64_t H, int64_t Wd) {
+    const char* W = "lava_conv_dgate";
+    TORCH_CHECK(dy.dim() == 4 && H >= 2 && Wd >= 2, W, ": dy must be [N, H / 2, W / 2, cout]");
+    const int64_t N = dy.size(0), cout = dy.size(3);
+    TORCH_CHECK(cin >= 32 && cin <= INT32_MAX && cout <= INT32_MAX && rt1_lava_conv_supported((int)cin, (int)cout), W,
+                ": (cin, cout) = (", cin, ", ", cout, ") is not a gated stage");
+    check_dev(y, "y", at::kBFloat16);
+    check_dev(dy, "dy", at::kBFloat16);
+    TORCH_CHECK(dy.sizes() == at::IntArrayRef({N, H / 2, Wd / 2, cout}) && y.sizes() == dy.sizes(), W,
+                ": dy / y have shapes ", dy.sizes(), " / ", y.sizes(), ", expected [N, H / 2, W / 2, cout]");
+    TORCH_CHECK(aligned16(dy) && aligned16(y) && y.device() == dy.device(), W,
+                ": dy / y misaligned or on different devices");
+    const float* gp = lava_conv_gate(W, &gate, dy, N, cin, cout);
+    at::Tensor dg = at::empty({N, cout}, gate.options());
+    check_launch(rt1_lava_conv_dgate(bf16_ptr(dy), bf16_ptr(y), gp, N, H, Wd, (int)cin, (int)cout,
+                                     dg.data_ptr<float>(), cur_stream()),
+                 W);
+    return dg;
+}
+
+// Tail of PixelLangMSE's encoder (csrc/kernels/lavapix.hip): y4 bf16 [N, hp, wp, 256], gate fp32 [N, 256], LayerNorm
+// weight / bias fp32 [256].
+void check_lava_pixel_tail(const char* W, const at::Tensor& y4, const at::Tensor& gate, const at::Tensor& ln_w) {
+    check_dev(y4, "y4", at::kBFloat16);
+    check_dev(gate, "gate", at::kFloat);
+    check_dev(ln_w, "ln_w", at::kFloat);
+    TORCH_CHECK(y4.dim() == 4 && y4.size(0) >= 1 && y4.size(1) >= 1 && y4.size(2) >= 1 && y4.size(3) <= INT32_MAX &&
+                    rt1_lava_pixel_tail_supported((int)y4.size(3)),
+                W, ": y4 must be [N, hp, wp, 256], got ", y4.sizes());
+    const int64_t N = y4.size(0), C = y4.size(3);
+    TORCH_CHECK(gate.sizes() == at::IntArrayRef({N, C}) && ln_w.numel() == C, W, ": gate must be [N, ", C,
+                "] and the LayerNorm weight [", C, "]");
+    TORCH_CHECK(aligned16(y4) && gate.device() == y4.device() && ln_w.device() == y4.device(), W,
+                ": y4 misaligned or tensors on different devices");
+}
+
+// -> (out [N, 256], mean [N, 256], stat [N, 2] = (mu, rstd)), fp32
+std::vector<at::Tensor> lava_pixel_tail_fwd(at::Tensor y4, at::Tensor gate, at::Tensor ln_w, at::Tensor ln_b,
+                                            double eps) {
+    const char* W = "lava_pixel_tail_fwd";
+    check_lava_pixel_tail(W, y4, gate, ln_w);
+    check_dev(ln_b, "ln_b", at::kFloat);
+    TORCH_CHECK(ln_b.numel() == ln_w.numel() && ln_b.device() == y4.device(), W, ": ln_b must match ln_w");
+    const int64_t N = y4.size(0), P = y4.size(1) * y4.size(2), C = y4.size(3);
+    const auto o = gate.options();
+    at::Tensor out = at::empty({N, C}, o), mean = at::empty({N, C}, o), stat = at::empty({N, 2}, o);
+    check_launch(rt1_lava_pixel_tail_fwd(bf16_ptr(y4), gate.data_ptr<float>(), ln_w.data_ptr<float>(),
+                                         ln_b.data_ptr<float>(), (float)eps, N, P, out.data_ptr<float>(),
+                                         mean.data_ptr<float>(), stat.data_ptr<float>(), cur_stream()),
+                 W);
+    return {out, mean, stat};
+}
+
+// -> (dy4 bf16 [N, hp, wp, 256], dgate [N, 256], dgamma [256], dbeta [256])
+std::vector<at::Tensor> lava_pixel_tail_bwd(at::Tensor dout, at::Tensor mean, at::Tensor stat, at::Tensor gate,
+                                            at::Tensor ln_w, int64_t hp, int64_t wp) {
+    const char* W = "lava_pixel_tail_bwd";
+    check_dev(dout, "dout", at::kFloat);
+    check_dev(mean, "mean", at::kFloat);
+    check_dev(stat, "stat", at::kFloat);
+    check_dev(gate, "gate", at::kFloat);
+    check_dev(ln_w, "ln_w", at::kFloat);
+    TORCH_CHECK(dout.dim() == 2 && dout.size(0) >= 1 && dout.size(1) <= INT32_MAX &&
+                    rt1_lava_pixel_tail_supported((int)dout.size(1)) && hp >= 1 && wp >= 1,
+                W, ": dout must be [N, 256] and hp, wp >= 1");
+    const int64_t N = dout.size(0), C = dout.size(1);
+    TORCH_CHECK(mean.sizes() == dout.sizes() && gate.sizes() == dout.sizes() &&
+                    stat.sizes() == at::IntArrayRef({N, 2}) && ln_w.numel() == C,
+                W, ": mean / gate must be [N, ", C, "], stat [N, 2] and the LayerNorm weight [", C, "]");
+    TORCH_CHECK(mean.device() == dout.device() && stat.device() == dout.device() && gate.device() == dout.device() &&
+                    ln_w.device() == dout.device(),
+                W, ": tensors on different devices");
+    const auto o = dout.options();
+    at::Tensor dy4 = at::empty({N, hp, wp, C}, o.dtype(at::kBFloat16)), dgate = at::empty({N, C}, o),
+               rows = at::empty({N, 2, C}, o), dgamma = at::empty({C}, o), dbeta = at::empty({C}, o);
+    check_launch(rt1_lava_pixel_tail_bwd(dout.data_ptr<float>(), mean.data_ptr<float>(), stat.data_ptr<float>(),
+                                         gate.data_ptr<float>(), ln_w.data_ptr<float>(), N, hp * wp, bf16_ptr(dy4),
+                                         dgate.data_ptr<float>(), rows.data_ptr<float>(), dgamma.data_ptr<float>(),
+                                         dbeta.data_ptr<float>(), cur_stream()),
+                 W);
+    return {dy4, dgate, dgamma, dbeta};
+}
+
+bool lava_pixel_tail_supported(int64_t channels) {
+    return channels > 0 && channels <= INT32_MAX && rt1_lava_pixel_tail_supported((int)channels);
 }
 
 bool lava_conv_supported(int64_t cin, int64_t cout) {
@@ -2354,6 +2484,17 @@ PYBIND11_MODULE(_rt1_hip, m) {
           "maxpool2(relu(conv3x3_same(x NHWC, weight) + bias)) -> (y bf16, idx uint8: 0..3 winner, 4 dead)");
     m.def("lava_conv_dgrad", &lava_conv_dgrad, "its data gradient from the pooled (dy, idx): -> dx bf16 [N, H, W, cin]");
     m.def("lava_conv_wgrad", &lava_conv_wgrad, "its weight and bias gradients from x and the pooled (dy, idx): fp32");
+    m.def("lava_conv_gated_fwd", &lava_conv_gated_fwd,
+          "maxpool2(relu(gate[n, c] * (conv3x3(x) + b))) -> (y bf16, idx uint8) [N, H/2, W/2, cout]; gate fp32 [N, cout]");
+    m.def("lava_conv_gated_dgrad", &lava_conv_gated_dgrad,
+          "its data gradient conv^T(bf16(dy * gate)) from the pooled (dy, idx): -> dx bf16 [N, H, W, cin]");
+    m.def("lava_conv_gated_wgrad", &lava_conv_gated_wgrad,
+          "its weight and bias gradients, the gate folded in once per frame in fp32");
+    m.def("lava_conv_dgate", &lava_conv_dgate, "its gate gradient (sum_p dy y) / gate from the stored y: fp32 [N, cout]");
+    m.def("lava_pixel_tail_supported", &lava_pixel_tail_supported, "whether the pixel-encoder tail serves this width");
+    m.def("lava_pixel_tail_fwd", &lava_pixel_tail_fwd,
+          "LayerNorm(relu(mean_p(y4) * gate)) -> (out, mean, stat = (mu, rstd)), fp32");
+    m.def("lava_pixel_tail_bwd", &lava_pixel_tail_bwd, "its backward: -> (dy4 bf16, dgate, dgamma, dbeta)");
     m.def("lava_sentence_supported", &lava_sentence_supported,
           "whether the lava_sentence kernels serve level channels (c2, c3) and d_model");
     m.def("lava_sentence_tile_rows", &lava_sentence_tile_rows, "sentence rows one workgroup owns");

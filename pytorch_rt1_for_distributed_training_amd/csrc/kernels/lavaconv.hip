@@ -2,9 +2,9 @@
 // Forward, data gradient and weight gradient as implicit GEMMs on v_mfma_f32_16x16x32_bf16; im2col, the
 // full-resolution conv output and the full-resolution pre-activation gradient dpre are never in memory.
 //
-// Shapes served: (Cin, Cout) in {(3, 32), (32, 64), (64, 128), (128, 256)}, any N, any H, W >= 2.  Activations and
-// their gradients are NHWC bf16, accumulation fp32, dW / db fp32.  The stage with Cin = 3 reads the frames as they
-// arrive, uint8 (/255 fused) or fp32, rounded to bf16 (RNE) while staging.
+// Shapes served: (Cin, Cout) in {(3 | 6 | 9 | 12, 32), (32, 64), (64, 128), (128, 256)}, any N, any H, W >= 2.
+// Activations and their gradients are NHWC bf16, accumulation fp32, dW / db fp32.  The first stage (Cin < 32) reads
+// the frames as they arrive, uint8 (/255 fused) or fp32, rounded to bf16 (RNE) while staging.
 //
 // Work split.  A 256-lane workgroup (4 waves) owns one frame's conv tile of kTh x kTw = 8 x 16 pixels (4 x 8 pooled)
 // and BN = 64 (or 32) output columns.  The 128 GEMM rows of the tile are numbered m = 4 * window + position (position
@@ -39,6 +39,14 @@
 // (16 interleaved chains per output, combined as a fixed tree) and writes dW in nn.Conv2d's [Cout][Cin][3][3].  No
 // atomics: dW, db are bitwise functions of the inputs.
 //
+// PixelLangMSE's language-conditioned encoder adds two forms (template parameters of the same kernels).  Its first
+// stage stacks s = 2 .. 4 frames channel-wise, Cin = 3 s in {6, 9, 12}: the im2col K = 9 Cin <= 108 is padded to 2 .. 4
+// chunks of 32 (the "taps" of the stage-1 kernels), the raw window row is 18 Cin consecutive values.  Its later stages
+// multiply conv + bias by a per-frame, per-channel gate g fp32 [N, Cout] before the ReLU (GATE): the forward epilogue
+// compares v = g * (acc + b); the data gradient rounds bf16(dy * g) while staging (K is the gated channel); the weight
+// gradient keeps dy as it is and folds g[frame, column] into a second fp32 accumulator when its item walk changes
+// frame; the gate gradient is a reduction of dy * y over the stage's own stored output (lava_conv_dgate_kernel).
+//
 // Every kernel is built without packed fp32 (common.h NO_PACKED_FP32); the bodies call only __forceinline__ functions.
 #include "common.h"
 
@@ -61,7 +69,17 @@ constexpr int kRs = 56;                           // raw (Cin = 3) window row st
 constexpr int X_ELEMS = kPix * kXs;               // 7200
 constexpr int R_ELEMS = kWh * kRs;                // 560
 constexpr int XV = (kPix * 4 + BLOCK - 1) / BLOCK;    // 16-byte window vectors per thread (3)
-constexpr int RV = (kWh * 54 + BLOCK - 1) / BLOCK;    // raw window values per thread (3)
+
+// first stage, Cin = 3 s stacked frames (s = 1 .. 4): a raw window row is kWw * Cin consecutive values, the im2col
+// tile has K = 9 Cin <= 108 zero padded to k_chunks(Cin) chunks of 32
+constexpr int r_vals(int cin) { return kWw * cin; }                                   // 54 at Cin = 3
+constexpr int r_stride(int cin) { return kWw * cin + 2; }                             // 56 = kRs
+constexpr int r_elems(int cin) { return kWh * r_stride(cin); }
+constexpr int r_regs(int cin) { return (kWh * r_vals(cin) + BLOCK - 1) / BLOCK; }     // raw values per thread (3 .. 9)
+constexpr int k_chunks(int cin) { return (9 * cin + 31) / 32; }
+constexpr int a_stride(int cin) { return k_chunks(cin) * 32 + 8; }                    // 40 = kXs
+constexpr int a_elems(int cin) { return cin == 3 ? X_ELEMS : kM * a_stride(cin); }
+static_assert(r_stride(3) == kRs && r_elems(3) == R_ELEMS && a_stride(3) == kXs, "Cin = 3 keeps its layout");
 
 enum Mode : int { FWD = 0, FWD1 = 1, DGRAD = 2 };
 
@@ -122,12 +140,22 @@ __device__ __forceinline__ void x_commit(const XRegs& R, bf16_t* Xl, int t) {
 }
 
 // the same window of dpre, expanded from the pooled (dy, idx) [*, Hp, Wp, C]
+// gated stage: the K dimension of the data gradient is the gated channel, so the operand is bf16_rne(dy * g[n, c]);
+// a thread's 8 channels are the same for all its window vectors (BLOCK % 4 == 0): one gate load per chunk
 struct DRegs {
     uint4 v[XV];
     uint2 ix[XV];
+    float4 g[2];
 };
+template <bool GATE>
 __device__ __forceinline__ void d_issue(DRegs& R, const bf16_t* __restrict__ dy, const uint8_t* __restrict__ idx,
-                                        int64_t n, int Hp, int Wp, int C, int h0, int w0, int kc, int t) {
+                                        const float* __restrict__ gate, int64_t n, int Hp, int Wp, int C, int h0,
+                                        int w0, int kc, int t) {
+    if constexpr (GATE) {
+        const float4* gp = reinterpret_cast<const float4*>(gate + n * C + kc * 32 + (t & 3) * 8);
+        R.g[0] = gp[0];
+        R.g[1] = gp[1];
+    }
 #pragma unroll
     for (int i = 0; i < XV; ++i) {
         const int item = t + i * BLOCK, pix = item >> 2, v = item & 3;
@@ -141,51 +169,65 @@ __device__ __forceinline__ void d_issue(DRegs& R, const bf16_t* __restrict__ dy,
         }
     }
 }
+template <bool GATE>
 __device__ __forceinline__ void d_commit(const DRegs& R, bf16_t* Xl, int h0, int w0, int t) {
 #pragma unroll
     for (int i = 0; i < XV; ++i) {
         const int item = t + i * BLOCK, pix = item >> 2;
         const int r = pix / kWw, c = pix - r * kWw, h = h0 - 1 + r, w = w0 - 1 + c;
-        if (item < kPix * 4)
-            *reinterpret_cast<uint4*>(Xl + pix * kXs + (item & 3) * 8) =
-                mask8(R.v[i], R.ix[i], (uint32_t)(((h & 1) << 1) | (w & 1)));
+        uint4 o = mask8(R.v[i], R.ix[i], (uint32_t)(((h & 1) << 1) | (w & 1)));
+        if constexpr (GATE) {                     // one fp32 multiply and one rounding (RNE) per element
+            float f[8];
+            unpack8(o, f);
+            o.x = pack2(f[0] * R.g[0].x, f[1] * R.g[0].y);
+            o.y = pack2(f[2] * R.g[0].z, f[3] * R.g[0].w);
+            o.z = pack2(f[4] * R.g[1].x, f[5] * R.g[1].y);
+            o.w = pack2(f[6] * R.g[1].z, f[7] * R.g[1].w);
+        }
+        if (item < kPix * 4) *reinterpret_cast<uint4*>(Xl + pix * kXs + (item & 3) * 8) = o;
     }
 }
 
-// raw window of the frames [*, H, W, 3] (uint8 / 255 or fp32): 54 consecutive values per window row
+// raw window of the frames [*, H, W, CIN] (uint8 / 255 or fp32): 18 * CIN consecutive values per window row
 __device__ __forceinline__ float frame_val(const uint8_t* p) { return (float)p[0] / 255.0f; }
 __device__ __forceinline__ float frame_val(const float* p) { return p[0]; }
 
+template <int CIN>
 struct RRegs {
-    float v[RV];
+    float v[r_regs(CIN)];
 };
-template <typename TIn>
-__device__ __forceinline__ void r_issue(RRegs& R, const TIn* __restrict__ img, int64_t n, int H, int W, int h0,
+template <int CIN, typename TIn>
+__device__ __forceinline__ void r_issue(RRegs<CIN>& R, const TIn* __restrict__ img, int64_t n, int H, int W, int h0,
                                         int w0, int t) {
+    constexpr int RW = r_vals(CIN);
 #pragma unroll
-    for (int i = 0; i < RV; ++i) {
-        const int item = t + i * BLOCK, r = item / 54, j = item - r * 54;
-        const int h = h0 - 1 + r, w = w0 - 1 + j / 3;
+    for (int i = 0; i < r_regs(CIN); ++i) {
+        const int item = t + i * BLOCK, r = item / RW, j = item - r * RW;
+        const int h = h0 - 1 + r, w = w0 - 1 + j / CIN;
         R.v[i] = 0.f;
-        if (item < kWh * 54 && h >= 0 && h < H && w >= 0 && w < W)
-            R.v[i] = frame_val(img + ((n * H + h) * W + w) * 3 + (j - (j / 3) * 3));
+        if (item < kWh * RW && h >= 0 && h < H && w >= 0 && w < W)
+            R.v[i] = frame_val(img + ((n * H + h) * W + w) * CIN + (j - (j / CIN) * CIN));
     }
 }
-// raw values -> LDS, then the im2col tile Al[m][k], k = tap * 3 + channel < 27, zero up to 32 (both barriers inside)
-__device__ __forceinline__ void r_commit_im2col(const RRegs& R, bf16_t* Rl, bf16_t* Al, int t) {
+// raw values -> LDS, then the im2col tile Al[m][k], k = tap * CIN + channel < 9 CIN, zero up to the chunk boundary
+// (both barriers inside).  A tap row of the window is 3 CIN consecutive raw values, but they start px * CIN values
+// into the row -- no 16-byte alignment for an A fragment read -- so the tile is built explicitly, value by value.
+template <int CIN>
+__device__ __forceinline__ void r_commit_im2col(const RRegs<CIN>& R, bf16_t* Rl, bf16_t* Al, int t) {
+    constexpr int RW = r_vals(CIN), RS = r_stride(CIN), KP = k_chunks(CIN) * 32, AS = a_stride(CIN);
 #pragma unroll
-    for (int i = 0; i < RV; ++i) {
-        const int item = t + i * BLOCK, r = item / 54, j = item - r * 54;
-        if (item < kWh * 54) Rl[r * kRs + j] = to_bf(R.v[i]);
+    for (int i = 0; i < r_regs(CIN); ++i) {
+        const int item = t + i * BLOCK, r = item / RW, j = item - r * RW;
+        if (item < kWh * RW) Rl[r * RS + j] = to_bf(R.v[i]);
     }
     block_sync();
 #pragma unroll
-    for (int i = 0; i < kM * 32 / BLOCK; ++i) {
-        const int item = t + i * BLOCK, m = item >> 5, k = item & 31;
+    for (int i = 0; i < kM * KP / BLOCK; ++i) {
+        const int item = t + i * BLOCK, m = item / KP, k = item - m * KP;
         int py, px;
         m2pix(m, py, px);
-        const int tap = k / 3, ch = k - tap * 3, dy = tap / 3, dx = tap - dy * 3;
-        Al[m * kXs + k] = k < 27 ? Rl[(py + dy) * kRs + (px + dx) * 3 + ch] : (bf16_t)0;
+        const int dy = k / (3 * CIN);             // k - dy * 3 CIN = dx * CIN + channel: consecutive in the raw row
+        Al[m * AS + k] = k < 9 * CIN ? Rl[(py + dy) * RS + px * CIN + (k - dy * 3 * CIN)] : (bf16_t)0;
     }
 }
 
@@ -196,17 +238,18 @@ struct BRegs {
     static constexpr int PER = (ITEMS + BLOCK - 1) / BLOCK;
     uint4 v[PER];
 };
-template <int TAPS, int BN>
+// FLAT (first stage): B is [Ktot][Ntot] and "tap" counts its chunks of 32 rows
+template <int TAPS, int BN, bool FLAT = false>
 __device__ __forceinline__ void b_issue(BRegs<TAPS, BN>& R, const bf16_t* __restrict__ B, int Ktot, int Ntot, int kc,
                                         int n0, int t) {
     constexpr int C8 = BN / 8;
 #pragma unroll
     for (int i = 0; i < BRegs<TAPS, BN>::PER; ++i) {
         const int item = t + i * BLOCK, tap = item / (32 * C8), rem = item - tap * (32 * C8);
-        const int k = rem / C8, c = (rem - k * C8) * 8, kg = kc * 32 + k;
+        const int k = rem / C8, c = (rem - k * C8) * 8, kg = FLAT ? tap * 32 + k : kc * 32 + k;
         R.v[i] = make_uint4(0, 0, 0, 0);
         if (item < BRegs<TAPS, BN>::ITEMS && kg < Ktot)
-            R.v[i] = *reinterpret_cast<const uint4*>(B + ((int64_t)tap * Ktot + kg) * Ntot + n0 + c);
+            R.v[i] = *reinterpret_cast<const uint4*>(B + ((int64_t)(FLAT ? 0 : tap) * Ktot + kg) * Ntot + n0 + c);
     }
 }
 template <int TAPS, int BN>
@@ -222,27 +265,32 @@ __device__ __forceinline__ void b_commit(const BRegs<TAPS, BN>& R, bf16_t* Bl, i
 // ---- forward and data gradient: one template ----------------------------------------------------------------------
 
 struct ConvArgs {
-    const void* x;            // FWD: bf16 [N, H, W, K]; FWD1: frames [N, H, W, 3]; DGRAD: dy bf16 [N, Hp, Wp, K]
+    const void* x;            // FWD: bf16 [N, H, W, K]; FWD1: frames [N, H, W, Cin]; DGRAD: dy bf16 [N, Hp, Wp, K]
     const uint8_t* idx_in;    // DGRAD: [N, Hp, Wp, K]
-    const bf16_t* B;          // packed weights [9][K][Nc] (FWD1: [27][Nc])
+    const bf16_t* B;          // packed weights [9][K][Nc] (FWD1: [9 Cin][Nc])
     const float* bias;        // FWD / FWD1: [Nc]
     bf16_t* y;                // FWD / FWD1: [N, Hp, Wp, Nc]; DGRAD: dx [N, H, W, Nc]
     uint8_t* idx_out;         // FWD / FWD1: [N, Hp, Wp, Nc]
     int H, W, Hp, Wp;         // conv grid and pooled grid
     int K, Nc;                // GEMM K per tap (input channels) and N (output channels)
     int tiles_x, tiles;       // tiles per row, tiles per frame
+    const float* gate;        // GATE: fp32 [N, gated channels]: y = pool(relu(g * (conv + b))), dx = conv^T(g * dpre)
 };
 
-template <int MODE, int NT, typename TIn>
+// GATE: the language-gated stage.  CIN1: the stacked-frame channels of the first stage (FWD1), whose "taps" are the
+// k_chunks(CIN1) chunks of the im2col K.
+template <int MODE, int NT, typename TIn, bool GATE = false, int CIN1 = 3>
 __global__ NO_PACKED_FP32 __launch_bounds__(BLOCK) void lava_conv_kernel(ConvArgs a) {
     constexpr int BN = NT * 16, LDB = BN + 8;
-    constexpr int TAPS = MODE == FWD1 ? 1 : 9;
+    constexpr int TAPS = MODE == FWD1 ? k_chunks(CIN1) : 9;
+    constexpr int AS = MODE == FWD1 ? a_stride(CIN1) : kXs;
+    constexpr int A_ELEMS = MODE == FWD1 ? a_elems(CIN1) : X_ELEMS;
     constexpr int B_ELEMS = TAPS * 32 * LDB;
     constexpr int O_ELEMS = MODE == DGRAD ? kM * LDB : 32 * LDB + 32 * (BN + 16) / 2;
-    constexpr int S_ELEMS = X_ELEMS + B_ELEMS + (MODE == FWD1 ? R_ELEMS : 0);
+    constexpr int S_ELEMS = A_ELEMS + B_ELEMS + (MODE == FWD1 ? r_elems(CIN1) : 0);
     __shared__ __attribute__((aligned(16))) bf16_t smem[S_ELEMS > O_ELEMS ? S_ELEMS : O_ELEMS];
     bf16_t* Xl = smem;
-    bf16_t* Bl = smem + X_ELEMS;
+    bf16_t* Bl = smem + A_ELEMS;
     bf16_t* Rl = Bl + B_ELEMS;
 
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, lr = lane & 15, lh = lane >> 4;
@@ -265,34 +313,35 @@ __global__ NO_PACKED_FP32 __launch_bounds__(BLOCK) void lava_conv_kernel(ConvArg
         const int m = (wave * 2 + i) * 16 + lr;
         int py, px;
         m2pix(m, py, px);
-        aoff[i] = (MODE == FWD1 ? m : py * kWw + px) * kXs + lh * 8;
+        aoff[i] = (MODE == FWD1 ? m : py * kWw + px) * AS + lh * 8;
     }
 
     XRegs xr;
     DRegs dr;
-    RRegs rr;
+    RRegs<CIN1> rr;
     BRegs<TAPS, BN> br;
     if constexpr (MODE == FWD) x_issue(xr, (const bf16_t*)a.x, n, a.H, a.W, a.K, h0, w0, 0, t);
-    if constexpr (MODE == DGRAD) d_issue(dr, (const bf16_t*)a.x, a.idx_in, n, a.Hp, a.Wp, a.K, h0, w0, 0, t);
-    if constexpr (MODE == FWD1) r_issue(rr, (const TIn*)a.x, n, a.H, a.W, h0, w0, t);
-    b_issue(br, a.B, MODE == FWD1 ? 27 : a.K, a.Nc, 0, n0, t);
+    if constexpr (MODE == DGRAD)
+        d_issue<GATE>(dr, (const bf16_t*)a.x, a.idx_in, a.gate, n, a.Hp, a.Wp, a.K, h0, w0, 0, t);
+    if constexpr (MODE == FWD1) r_issue<CIN1>(rr, (const TIn*)a.x, n, a.H, a.W, h0, w0, t);
+    b_issue<TAPS, BN, MODE == FWD1>(br, a.B, MODE == FWD1 ? 9 * CIN1 : a.K, a.Nc, 0, n0, t);
 
     for (int kc = 0; kc < nch; ++kc) {
         block_sync();                              // the previous chunk's fragment reads are done
         if constexpr (MODE == FWD) x_commit(xr, Xl, t);
-        if constexpr (MODE == DGRAD) d_commit(dr, Xl, h0, w0, t);
-        if constexpr (MODE == FWD1) r_commit_im2col(rr, Rl, Xl, t);
+        if constexpr (MODE == DGRAD) d_commit<GATE>(dr, Xl, h0, w0, t);
+        if constexpr (MODE == FWD1) r_commit_im2col<CIN1>(rr, Rl, Xl, t);
         b_commit(br, Bl, t);
         block_sync();
         if (kc + 1 < nch) {                        // in flight during this chunk's MFMAs
             if constexpr (MODE == FWD) x_issue(xr, (const bf16_t*)a.x, n, a.H, a.W, a.K, h0, w0, kc + 1, t);
             if constexpr (MODE == DGRAD)
-                d_issue(dr, (const bf16_t*)a.x, a.idx_in, n, a.Hp, a.Wp, a.K, h0, w0, kc + 1, t);
+                d_issue<GATE>(dr, (const bf16_t*)a.x, a.idx_in, a.gate, n, a.Hp, a.Wp, a.K, h0, w0, kc + 1, t);
             b_issue(br, a.B, a.K, a.Nc, kc + 1, n0, t);
         }
 #pragma unroll
         for (int tap = 0; tap < TAPS; ++tap) {
-            const int toff = MODE == FWD1 ? 0 : ((tap / 3) * kWw + (tap % 3)) * kXs;
+            const int toff = MODE == FWD1 ? tap * 32 : ((tap / 3) * kWw + (tap % 3)) * kXs;
             bf16x8 fa[2];
 #pragma unroll
             for (int i = 0; i < 2; ++i) fa[i] = *reinterpret_cast<const bf16x8*>(Xl + aoff[i] + toff);
@@ -337,13 +386,20 @@ __global__ NO_PACKED_FP32 __launch_bounds__(BLOCK) void lava_conv_kernel(ConvArg
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
             const float bv = a.bias[n0 + j * 16 + lr];
+            float gv = 1.f;
+            if constexpr (GATE) gv = a.gate[n * a.Nc + n0 + j * 16 + lr];
+            // gated: v = g * (conv + b) in fp32; a negative gate makes the smallest conv value win, a zero gate
+            // leaves no v > 0: the whole channel of the frame is dead
+            auto cand = [&](int i, int e) __attribute__((always_inline)) {
+                return GATE ? gv * (acc[i][j][e] + bv) : acc[i][j][e] + bv;
+            };
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
-                float best = acc[i][j][0] + bv;
+                float best = cand(i, 0);
                 int bi = 0;
 #pragma unroll
                 for (int e = 1; e < 4; ++e) {
-                    const float v = acc[i][j][e] + bv;
+                    const float v = cand(i, e);
                     if (v > best) {                // a tie keeps the lowest position
                         best = v;
                         bi = e;
@@ -379,7 +435,7 @@ __global__ NO_PACKED_FP32 __launch_bounds__(BLOCK) void lava_conv_kernel(ConvArg
 // ---- weight gradient ----------------------------------------------------------------------------------------------
 
 struct WgradArgs {
-    const void* x;            // bf16 [N, H, W, Cin] or the frames [N, H, W, 3]
+    const void* x;            // bf16 [N, H, W, Cin] or the frames [N, H, W, Cin < 32]
     const bf16_t* dy;         // [N, Hp, Wp, Cout]
     const uint8_t* idx;       // [N, Hp, Wp, Cout]
     float* part;              // [P][9 * Cin][Cout]
@@ -388,17 +444,23 @@ struct WgradArgs {
     int tiles_x, tiles;
     int64_t T;                // N * tiles work items, split into P contiguous ranges
     int P;
+    const float* gate;        // GATE: fp32 [N, Cout]: dW = sum_n g[n, :] * (patch_n^T dpre_n), db likewise
 };
 
-// IM2COL (Cin = 3): A^T is the im2col tile [128 pixels][27 -> 32], one "tap", wave = (row tile, column tile) of
-// [32][32]; otherwise A^T is the staged window read tap-shifted, wave = column tile of [9][32][64], both row tiles.
-template <bool IM2COL, typename TIn>
+// IM2COL (first stage, CIN1 = 3 s): A^T is the im2col tile [128 pixels][k_chunks x 32], a "tap" is one chunk of 32
+// rows, wave = (row tile, column tile) of [32][32] per chunk; otherwise A^T is the staged window read tap-shifted,
+// wave = column tile of [9][32][64], both row tiles.
+// GATE: the gate is per output column and a lane's accumulator columns are fixed, so dy is not re-rounded: acc is the
+// running sum of ONE frame, folded into tot as tot += g[frame, column] * acc (fp32) when the item walk enters
+// another frame and at the end.
+template <bool IM2COL, typename TIn, bool GATE = false, int CIN1 = 3>
 __global__ NO_PACKED_FP32 __launch_bounds__(BLOCK) void lava_conv_wgrad_kernel(WgradArgs a) {
-    constexpr int TAPS = IM2COL ? 1 : 9, MTW = IM2COL ? 1 : 2, CoT = IM2COL ? 32 : 64, DS = CoT + 8;
+    constexpr int TAPS = IM2COL ? k_chunks(CIN1) : 9, MTW = IM2COL ? 1 : 2, CoT = IM2COL ? 32 : 64, DS = CoT + 8;
+    constexpr int AS = IM2COL ? a_stride(CIN1) : kXs, A_ELEMS = IM2COL ? a_elems(CIN1) : X_ELEMS;
     constexpr int D_ELEMS = kM * DS;
-    __shared__ __attribute__((aligned(16))) bf16_t smem[X_ELEMS + D_ELEMS + (IM2COL ? R_ELEMS : 0)];
+    __shared__ __attribute__((aligned(16))) bf16_t smem[A_ELEMS + D_ELEMS + (IM2COL ? r_elems(CIN1) : 0)];
     bf16_t* Xl = smem;
-    bf16_t* Dl = smem + X_ELEMS;
+    bf16_t* Dl = smem + A_ELEMS;
     bf16_t* Rl = Dl + D_ELEMS;
 
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, lr = lane & 15, lh = lane >> 4;
@@ -410,10 +472,14 @@ __global__ NO_PACKED_FP32 __launch_bounds__(BLOCK) void lava_conv_wgrad_kernel(W
     const bool do_db = blockIdx.y == 0 && rt0 == 0;
 
     f32x4 acc[TAPS][MTW], accdb = f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 tot[GATE ? TAPS : 1][MTW], totdb = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int i = 0; i < TAPS; ++i)
 #pragma unroll
-        for (int j = 0; j < MTW; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < MTW; ++j) {
+            acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if constexpr (GATE) tot[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
     const short one = (short)0x3f80;
     const bf16x8 ones = bf16x8{one, one, one, one, one, one, one, one};
 
@@ -422,7 +488,7 @@ __global__ NO_PACKED_FP32 __launch_bounds__(BLOCK) void lava_conv_wgrad_kernel(W
     const int dwi = t / (CoT / 8), dv = t - dwi * (CoT / 8);
 
     XRegs xr;
-    RRegs rr;
+    RRegs<CIN1> rr;
     uint4 dyv;
     uint2 dix;
     int64_t n;
@@ -432,7 +498,7 @@ __global__ NO_PACKED_FP32 __launch_bounds__(BLOCK) void lava_conv_wgrad_kernel(W
         const int tile = (int)(item - n * a.tiles), ty = tile / a.tiles_x, tx = tile - ty * a.tiles_x;
         h0 = ty * kTh;
         w0 = tx * kTw;
-        if constexpr (IM2COL) r_issue(rr, (const TIn*)a.x, n, a.H, a.W, h0, w0, t);
+        if constexpr (IM2COL) r_issue<CIN1>(rr, (const TIn*)a.x, n, a.H, a.W, h0, w0, t);
         else x_issue(xr, (const bf16_t*)a.x, n, a.H, a.W, a.Cin, h0, w0, blockIdx.y, t);
         dyv = make_uint4(0, 0, 0, 0);
         dix = make_uint2(0x04040404u, 0x04040404u);
@@ -443,11 +509,32 @@ __global__ NO_PACKED_FP32 __launch_bounds__(BLOCK) void lava_conv_wgrad_kernel(W
             dix = *reinterpret_cast<const uint2*>(a.idx + off);
         }
     };
+    auto fold = [&](int64_t frame) __attribute__((always_inline)) {
+        const float gv = a.gate[frame * a.Cout + co0 + ct * 16 + lr];
+#pragma unroll
+        for (int i = 0; i < TAPS; ++i)
+#pragma unroll
+            for (int j = 0; j < MTW; ++j)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    tot[GATE ? i : 0][j][e] += gv * acc[i][j][e];
+                    acc[i][j][e] = 0.f;
+                }
+        totdb[0] += gv * accdb[0];
+        accdb = f32x4{0.f, 0.f, 0.f, 0.f};
+    };
     issue(t0);
+    int64_t nacc = n;                             // the frame acc belongs to
     for (int64_t item = t0; item < t1; ++item) {
         block_sync();
-        if constexpr (IM2COL) r_commit_im2col(rr, Rl, Xl, t);
+        if constexpr (IM2COL) r_commit_im2col<CIN1>(rr, Rl, Xl, t);
         else x_commit(xr, Xl, t);
+        if constexpr (GATE) {                     // n is still this item's frame: the next issue comes below
+            if (n != nacc) {
+                fold(nacc);
+                nacc = n;
+            }
+        }
         if (t < DV) {
 #pragma unroll
             for (int pos = 0; pos < 4; ++pos)
@@ -463,11 +550,11 @@ __global__ NO_PACKED_FP32 __launch_bounds__(BLOCK) void lava_conv_wgrad_kernel(W
             int pya, pxa, pyb, pxb;
             m2pix(ma, pya, pxa);
             m2pix(mb, pyb, pxb);
-            const int xa = (IM2COL ? ma : pya * kWw + pxa) * kXs + p4 * 4;
-            const int xb = (IM2COL ? mb : pyb * kWw + pxb) * kXs + p4 * 4;
+            const int xa = (IM2COL ? ma : pya * kWw + pxa) * AS + p4 * 4;
+            const int xb = (IM2COL ? mb : pyb * kWw + pxb) * AS + p4 * 4;
 #pragma unroll
             for (int tap = 0; tap < TAPS; ++tap) {
-                const int toff = IM2COL ? 0 : ((tap / 3) * kWw + (tap % 3)) * kXs;
+                const int toff = IM2COL ? tap * 32 : ((tap / 3) * kWw + (tap % 3)) * kXs;
 #pragma unroll
                 for (int i = 0; i < MTW; ++i) {
                     const int co = toff + (rt0 + i) * 16;
@@ -478,8 +565,11 @@ __global__ NO_PACKED_FP32 __launch_bounds__(BLOCK) void lava_conv_wgrad_kernel(W
         }
     }
 
-    // lane holds rows (rt0 + i) * 16 + lh * 4 + e (input channel, or tap * 3 + channel) of column ct * 16 + lr
-    const int rows = IM2COL ? 27 : 9 * a.Cin;
+    if constexpr (GATE) fold(nacc);
+
+    // lane holds rows (rt0 + i) * 16 + lh * 4 + e (input channel, or chunk * 32 + ... = tap * Cin + channel) of
+    // column ct * 16 + lr
+    const int rows = IM2COL ? 9 * CIN1 : 9 * a.Cin;
     float* part = a.part + p * rows * a.Cout + co0 + ct * 16 + lr;
 #pragma unroll
     for (int tap = 0; tap < TAPS; ++tap)
@@ -488,10 +578,60 @@ __global__ NO_PACKED_FP32 __launch_bounds__(BLOCK) void lava_conv_wgrad_kernel(W
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const int r = (rt0 + i) * 16 + lh * 4 + e;
-                const int row = IM2COL ? r : tap * a.Cin + ci0 + r;
-                if (row < rows) part[(int64_t)row * a.Cout] = acc[tap][i][e];
+                const int row = IM2COL ? tap * 32 + r : tap * a.Cin + ci0 + r;
+                if (row < rows) part[(int64_t)row * a.Cout] = GATE ? tot[GATE ? tap : 0][i][e] : acc[tap][i][e];
             }
-    if (do_db && lh == 0) a.dbpart[p * a.Cout + co0 + ct * 16 + lr] = accdb[0];
+    if (do_db && lh == 0) a.dbpart[p * a.Cout + co0 + ct * 16 + lr] = GATE ? totdb[0] : accdb[0];
+}
+
+// Gate gradient of a gated stage.  At a live winner y = g * (conv + b) and y is stored (it is the next stage's
+// input), so dg[n, c] = (sum_p dy[n, p, c] * y[n, p, c]) / g[n, c], 0 where g == 0; a dead window has y = 0.  No conv
+// is recomputed.  Workgroup = (frame, slab of 64 channels): 8 channel vectors x 32 pixel lanes, four 16-byte loads
+// of dy and of y in flight per lane, fp32 sums, the 32 lanes combined as a fixed tree: bitwise reproducible.
+__global__ NO_PACKED_FP32 __launch_bounds__(BLOCK) void lava_conv_dgate_kernel(
+    const bf16_t* __restrict__ dy, const bf16_t* __restrict__ y, const float* __restrict__ gate, int P, int C,
+    float* __restrict__ dg) {
+    __shared__ float red[32][64 + 1];
+    const int t = threadIdx.x, cv = t & 7, pl = t >> 3;
+    const int64_t n = blockIdx.x;
+    const int c0 = blockIdx.y * 64;
+    const int64_t base = n * P * C + c0 + cv * 8;
+    float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int p0 = pl; p0 < P; p0 += 128) {
+        uint4 a[4], b[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int p = p0 + 32 * u;
+            a[u] = b[u] = make_uint4(0, 0, 0, 0);
+            if (p < P) {
+                a[u] = *reinterpret_cast<const uint4*>(dy + base + (int64_t)p * C);
+                b[u] = *reinterpret_cast<const uint4*>(y + base + (int64_t)p * C);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            float fa[8], fb[8];
+            unpack8(a[u], fa);
+            unpack8(b[u], fb);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) s[e] += fa[e] * fb[e];
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) red[pl][cv * 8 + e] = s[e];
+    block_sync();
+    if (t < 64) {
+        float q[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            float v = 0.f;
+#pragma unroll
+            for (int r = 0; r < 8; ++r) v += red[u * 8 + r][t];
+            q[u] = v;
+        }
+        const float g = gate[n * C + c0 + t];
+        dg[n * C + c0 + t] = g == 0.f ? 0.f : ((q[0] + q[1]) + (q[2] + q[3])) / g;
+    }
 }
 
 // partials in a fixed order -> dW fp32 [Cout][Cin][3][3] and db fp32 [Cout]
@@ -538,8 +678,8 @@ struct Geo {
 
 // false when a shape cannot be served (or a launch dimension would overflow)
 bool geometry(int64_t N, int64_t H, int64_t W, int cin, int cout, Geo& g) {
-    if (!((cin == 3 && cout == 32) || (cin == 32 && cout == 64) || (cin == 64 && cout == 128) ||
-          (cin == 128 && cout == 256)))
+    const bool first = (cin == 3 || cin == 6 || cin == 9 || cin == 12) && cout == 32;      // 1 .. 4 stacked frames
+    if (!(first || (cin == 32 && cout == 64) || (cin == 64 && cout == 128) || (cin == 128 && cout == 256)))
         return false;
     if (N < 1 || H < 2 || W < 2 || H > (1 << 20) || W > (1 << 20)) return false;
     g.Hp = (int)(H / 2);
@@ -552,16 +692,98 @@ bool geometry(int64_t N, int64_t H, int64_t W, int cin, int cout, Geo& g) {
     return g.blocks <= INT32_MAX;
 }
 
-template <int MODE, int NT, typename TIn>
+template <int MODE, int NT, typename TIn, bool GATE = false, int CIN1 = 3>
 void launch_conv(const ConvArgs& a, int64_t blocks, hipStream_t st) {
-    hipLaunchKernelGGL((lava_conv_kernel<MODE, NT, TIn>), dim3((unsigned)blocks, (unsigned)(a.Nc / (NT * 16))),
-                       dim3(BLOCK), 0, st, a);
+    hipLaunchKernelGGL((lava_conv_kernel<MODE, NT, TIn, GATE, CIN1>),
+                       dim3((unsigned)blocks, (unsigned)(a.Nc / (NT * 16))), dim3(BLOCK), 0, st, a);
+}
+
+template <typename TIn>
+void launch_fwd1(const ConvArgs& a, int64_t blocks, int cin, hipStream_t st) {
+    if (cin == 3) launch_conv<FWD1, 2, TIn, false, 3>(a, blocks, st);
+    else if (cin == 6) launch_conv<FWD1, 2, TIn, false, 6>(a, blocks, st);
+    else if (cin == 9) launch_conv<FWD1, 2, TIn, false, 9>(a, blocks, st);
+    else launch_conv<FWD1, 2, TIn, false, 12>(a, blocks, st);
+}
+
+template <typename TIn, int CIN1>
+void launch_wgrad1(const WgradArgs& a, hipStream_t st) {
+    hipLaunchKernelGGL((lava_conv_wgrad_kernel<true, TIn, false, CIN1>), dim3(a.P, 1, 1), dim3(BLOCK), 0, st, a);
+}
+template <typename TIn>
+void launch_wgrad1(const WgradArgs& a, hipStream_t st) {
+    if (a.Cin == 3) launch_wgrad1<TIn, 3>(a, st);
+    else if (a.Cin == 6) launch_wgrad1<TIn, 6>(a, st);
+    else if (a.Cin == 9) launch_wgrad1<TIn, 9>(a, st);
+    else launch_wgrad1<TIn, 12>(a, st);
 }
 
 int wgrad_partials(const Geo& g, int cin, int cout) {
-    const int ctiles = cin == 3 ? 1 : (cin / 32) * (cout / 64);
+    const int ctiles = cin < 32 ? 1 : (cin / 32) * (cout / 64);
     const int64_t cap = 1024 / ctiles;             // about four workgroups per CU over all channel tiles
     return (int)(g.blocks < cap ? g.blocks : cap);
+}
+
+// x_kind: 0 = bf16 NHWC activations, 1 = uint8 frames, 2 = fp32 frames (1, 2 only with Cin < 32 and the reverse);
+// gate: nullptr for the plain stage, else fp32 [N, cout] (Cin >= 32 only)
+bool kind_ok(int cin, int x_kind, const float* gate) {
+    return x_kind >= 0 && x_kind <= 2 && (cin < 32) == (x_kind != 0) && (gate == nullptr || cin >= 32);
+}
+
+int conv_fwd(const void* x, int x_kind, const uint16_t* wp, const float* bias, const float* gate, int64_t N, int64_t H,
+             int64_t W, int cin, int cout, uint16_t* y, uint8_t* idx, hipStream_t stream) {
+    Geo g;
+    if (x == nullptr || wp == nullptr || bias == nullptr || y == nullptr || idx == nullptr ||
+        !geometry(N, H, W, cin, cout, g) || !kind_ok(cin, x_kind, gate))
+        return (int)hipErrorInvalidValue;
+    ConvArgs a{x, nullptr, wp, bias, y, idx, (int)H, (int)W, g.Hp, g.Wp, cin, cout, g.tiles_x,
+               g.tiles_x * g.tiles_y, gate};
+    if (x_kind == 1) launch_fwd1<uint8_t>(a, g.blocks, cin, stream);
+    else if (x_kind == 2) launch_fwd1<float>(a, g.blocks, cin, stream);
+    else if (gate != nullptr) launch_conv<FWD, 4, uint16_t, true>(a, g.blocks, stream);
+    else launch_conv<FWD, 4, uint16_t>(a, g.blocks, stream);
+    return (int)hipGetLastError();
+}
+
+int conv_dgrad(const uint16_t* dy, const uint8_t* idx, const uint16_t* wd, const float* gate, int64_t N, int64_t H,
+               int64_t W, int cin, int cout, uint16_t* dx, hipStream_t stream) {
+    Geo g;
+    if (dy == nullptr || idx == nullptr || wd == nullptr || dx == nullptr || !geometry(N, H, W, cin, cout, g) ||
+        cin < 32)
+        return (int)hipErrorInvalidValue;
+    ConvArgs a{dy, idx, wd, nullptr, dx, nullptr, (int)H, (int)W, g.Hp, g.Wp, cout, cin, g.tiles_x,
+               g.tiles_x * g.tiles_y, gate};
+    if (gate != nullptr) {
+        if (cin == 32) launch_conv<DGRAD, 2, uint16_t, true>(a, g.blocks, stream);
+        else launch_conv<DGRAD, 4, uint16_t, true>(a, g.blocks, stream);
+    } else {
+        if (cin == 32) launch_conv<DGRAD, 2, uint16_t>(a, g.blocks, stream);
+        else launch_conv<DGRAD, 4, uint16_t>(a, g.blocks, stream);
+    }
+    return (int)hipGetLastError();
+}
+
+int conv_wgrad(const void* x, int x_kind, const uint16_t* dy, const uint8_t* idx, const float* gate, int64_t N,
+               int64_t H, int64_t W, int cin, int cout, float* part, float* dbpart, float* dW, float* db,
+               hipStream_t stream) {
+    Geo g;
+    if (x == nullptr || dy == nullptr || idx == nullptr || part == nullptr || dbpart == nullptr || dW == nullptr ||
+        db == nullptr || !geometry(N, H, W, cin, cout, g) || !kind_ok(cin, x_kind, gate))
+        return (int)hipErrorInvalidValue;
+    const int P = wgrad_partials(g, cin, cout);
+    WgradArgs a{x, dy, idx, part, dbpart, (int)H, (int)W, g.Hp, g.Wp, cin, cout, g.tiles_x, g.tiles_x * g.tiles_y,
+                g.blocks, P, gate};
+    const dim3 grid(P, cin / 32, cout / 64);
+    if (x_kind == 1) launch_wgrad1<uint8_t>(a, stream);
+    else if (x_kind == 2) launch_wgrad1<float>(a, stream);
+    else if (gate != nullptr)
+        hipLaunchKernelGGL((lava_conv_wgrad_kernel<false, uint16_t, true>), grid, dim3(BLOCK), 0, stream, a);
+    else
+        hipLaunchKernelGGL((lava_conv_wgrad_kernel<false, uint16_t>), grid, dim3(BLOCK), 0, stream, a);
+    const int E = 9 * cin * cout + cout;
+    hipLaunchKernelGGL(lava_conv_wgrad_reduce_kernel, dim3((E + 63) / 64), dim3(BLOCK), 0, stream, part,
+                       dbpart, P, cin, cout, dW, db);
+    return (int)hipGetLastError();
 }
 
 }  // namespace
@@ -574,34 +796,16 @@ extern "C" int rt1_lava_conv_supported(int cin, int cout) {
 extern "C" int rt1_lava_conv_tile_h() { return kTh; }
 extern "C" int rt1_lava_conv_tile_w() { return kTw; }
 
-// x_kind: 0 = bf16 NHWC activations, 1 = uint8 frames, 2 = fp32 frames (1, 2 only with Cin = 3 and the reverse)
 extern "C" int rt1_lava_conv_fwd(const void* x, int x_kind, const uint16_t* wp, const float* bias, int64_t N,
                                  int64_t H, int64_t W, int cin, int cout, uint16_t* y, uint8_t* idx,
                                  hipStream_t stream) {
-    Geo g;
-    if (x == nullptr || wp == nullptr || bias == nullptr || y == nullptr || idx == nullptr ||
-        !geometry(N, H, W, cin, cout, g) || (cin == 3) != (x_kind != 0) || x_kind < 0 || x_kind > 2)
-        return (int)hipErrorInvalidValue;
-    ConvArgs a{x, nullptr, wp, bias, y, idx, (int)H, (int)W, g.Hp, g.Wp, cin, cout, g.tiles_x,
-               g.tiles_x * g.tiles_y};
-    if (x_kind == 1) launch_conv<FWD1, 2, uint8_t>(a, g.blocks, stream);
-    else if (x_kind == 2) launch_conv<FWD1, 2, float>(a, g.blocks, stream);
-    else launch_conv<FWD, 4, uint16_t>(a, g.blocks, stream);
-    return (int)hipGetLastError();
+    return conv_fwd(x, x_kind, wp, bias, nullptr, N, H, W, cin, cout, y, idx, stream);
 }
 
 // dx [N, H, W, cin] of a stage with cin >= 32; wd = the weights flipped and transposed, [9][cout][cin]
 extern "C" int rt1_lava_conv_dgrad(const uint16_t* dy, const uint8_t* idx, const uint16_t* wd, int64_t N, int64_t H,
                                    int64_t W, int cin, int cout, uint16_t* dx, hipStream_t stream) {
-    Geo g;
-    if (dy == nullptr || idx == nullptr || wd == nullptr || dx == nullptr || !geometry(N, H, W, cin, cout, g) ||
-        cin == 3)
-        return (int)hipErrorInvalidValue;
-    ConvArgs a{dy, idx, wd, nullptr, dx, nullptr, (int)H, (int)W, g.Hp, g.Wp, cout, cin, g.tiles_x,
-               g.tiles_x * g.tiles_y};
-    if (cin == 32) launch_conv<DGRAD, 2, uint16_t>(a, g.blocks, stream);
-    else launch_conv<DGRAD, 4, uint16_t>(a, g.blocks, stream);
-    return (int)hipGetLastError();
+    return conv_dgrad(dy, idx, wd, nullptr, N, H, W, cin, cout, dx, stream);
 }
 
 // workgroup partials of the weight gradient: a function of the shape alone, 0 for an unserved one
@@ -614,22 +818,39 @@ extern "C" int64_t rt1_lava_conv_wgrad_partials(int64_t N, int64_t H, int64_t W,
 extern "C" int rt1_lava_conv_wgrad(const void* x, int x_kind, const uint16_t* dy, const uint8_t* idx, int64_t N,
                                    int64_t H, int64_t W, int cin, int cout, float* part, float* dbpart, float* dW,
                                    float* db, hipStream_t stream) {
+    return conv_wgrad(x, x_kind, dy, idx, nullptr, N, H, W, cin, cout, part, dbpart, dW, db, stream);
+}
+
+// the language-gated stage (cin >= 32), gate fp32 [N, cout]: y = maxpool2(relu(gate[n, c] * (conv(x) + b)))
+extern "C" int rt1_lava_conv_gated_fwd(const uint16_t* x, const uint16_t* wp, const float* bias, const float* gate,
+                                       int64_t N, int64_t H, int64_t W, int cin, int cout, uint16_t* y, uint8_t* idx,
+                                       hipStream_t stream) {
+    if (gate == nullptr) return (int)hipErrorInvalidValue;
+    return conv_fwd(x, 0, wp, bias, gate, N, H, W, cin, cout, y, idx, stream);
+}
+
+extern "C" int rt1_lava_conv_gated_dgrad(const uint16_t* dy, const uint8_t* idx, const uint16_t* wd,
+                                         const float* gate, int64_t N, int64_t H, int64_t W, int cin, int cout,
+                                         uint16_t* dx, hipStream_t stream) {
+    if (gate == nullptr) return (int)hipErrorInvalidValue;
+    return conv_dgrad(dy, idx, wd, gate, N, H, W, cin, cout, dx, stream);
+}
+
+extern "C" int rt1_lava_conv_gated_wgrad(const uint16_t* x, const uint16_t* dy, const uint8_t* idx, const float* gate,
+                                         int64_t N, int64_t H, int64_t W, int cin, int cout, float* part,
+                                         float* dbpart, float* dW, float* db, hipStream_t stream) {
+    if (gate == nullptr) return (int)hipErrorInvalidValue;
+    return conv_wgrad(x, 0, dy, idx, gate, N, H, W, cin, cout, part, dbpart, dW, db, stream);
+}
+
+// dgate fp32 [N, cout] from the pooled dy and the stage's own stored output y, both bf16 [N, H / 2, W / 2, cout]
+extern "C" int rt1_lava_conv_dgate(const uint16_t* dy, const uint16_t* y, const float* gate, int64_t N, int64_t H,
+                                   int64_t W, int cin, int cout, float* dgate, hipStream_t stream) {
     Geo g;
-    if (x == nullptr || dy == nullptr || idx == nullptr || part == nullptr || dbpart == nullptr || dW == nullptr ||
-        db == nullptr || !geometry(N, H, W, cin, cout, g) || (cin == 3) != (x_kind != 0) || x_kind < 0 || x_kind > 2)
+    if (dy == nullptr || y == nullptr || gate == nullptr || dgate == nullptr || !geometry(N, H, W, cin, cout, g) ||
+        cin < 32 || (int64_t)g.Hp * g.Wp > INT32_MAX)
         return (int)hipErrorInvalidValue;
-    const int P = wgrad_partials(g, cin, cout);
-    WgradArgs a{x, dy, idx, part, dbpart, (int)H, (int)W, g.Hp, g.Wp, cin, cout, g.tiles_x, g.tiles_x * g.tiles_y,
-                g.blocks, P};
-    if (x_kind == 1)
-        hipLaunchKernelGGL((lava_conv_wgrad_kernel<true, uint8_t>), dim3(P, 1, 1), dim3(BLOCK), 0, stream, a);
-    else if (x_kind == 2)
-        hipLaunchKernelGGL((lava_conv_wgrad_kernel<true, float>), dim3(P, 1, 1), dim3(BLOCK), 0, stream, a);
-    else
-        hipLaunchKernelGGL((lava_conv_wgrad_kernel<false, uint16_t>), dim3(P, cin / 32, cout / 64), dim3(BLOCK), 0,
-                           stream, a);
-    const int E = 9 * cin * cout + cout;
-    hipLaunchKernelGGL(lava_conv_wgrad_reduce_kernel, dim3((E + 63) / 64), dim3(BLOCK), 0, stream, part,
-                       dbpart, P, cin, cout, dW, db);
+    hipLaunchKernelGGL(lava_conv_dgate_kernel, dim3((unsigned)N, cout / 64), dim3(BLOCK), 0, stream, dy, y, gate,
+                       g.Hp * g.Wp, cout, dgate);
     return (int)hipGetLastError();
 }

@@ -76,9 +76,9 @@ int rt1_lava_xattn_bwd(const float* dctx, const float* pix, const float* Q, cons
                        hipStream_t stream);
 
 // lavaconv.hip: one LAVA image-encoder stage, y = maxpool2(relu(conv3x3_same(x, W) + b)) with VALID pooling, as
-// implicit-GEMM MFMA kernels; (cin, cout) in {(3, 32), (32, 64), (64, 128), (128, 256)}, H, W >= 2.  Activations and
-// their gradients are NHWC bf16 (raw uint16_t here), the pooled grid is [H / 2, W / 2].  x_kind: 0 = bf16
-// activations (cin >= 32), 1 = uint8 frames (/255), 2 = fp32 frames (cin = 3).
+// implicit-GEMM MFMA kernels; (cin, cout) in {(3 s, 32) for s = 1 .. 4 stacked frames, (32, 64), (64, 128),
+// (128, 256)}, H, W >= 2.  Activations and their gradients are NHWC bf16 (raw uint16_t here), the pooled grid is
+// [H / 2, W / 2].  x_kind: 0 = bf16 activations (cin >= 32), 1 = uint8 frames (/255), 2 = fp32 frames (cin < 32).
 //   fwd    wp bf16 [9][cin][cout], bias fp32 [cout] -> y bf16 and idx uint8 [N, H/2, W/2, cout]; idx 0..3 = the
 //          winning window position (row-major, ties to the lowest), 4 = dead (window max <= 0, y = 0)
 //   dgrad  (dy, idx) and wd bf16 [9][cout][cin] (flipped, transposed) -> dx bf16 [N, H, W, cin]; cin >= 32
@@ -95,6 +95,29 @@ int64_t rt1_lava_conv_wgrad_partials(int64_t N, int64_t H, int64_t W, int cin, i
 int rt1_lava_conv_wgrad(const void* x, int x_kind, const uint16_t* dy, const uint8_t* idx, int64_t N, int64_t H,
                         int64_t W, int cin, int cout, float* part, float* dbpart, float* dW, float* db,
                         hipStream_t stream);
+// The language-gated stage (cin >= 32), gate fp32 [N, cout]: y = maxpool2(relu(gate[n, c] * (conv(x) + b))); dead =
+// no gated candidate > 0.  dgrad forms the operand bf16_rne(dy * gate) while staging; wgrad folds gate[n, :] into the
+// fp32 accumulators once per frame; dgate [N, cout] = (sum_p dy * y) / gate from the stage's own stored y, 0 where
+// gate == 0.
+int rt1_lava_conv_gated_fwd(const uint16_t* x, const uint16_t* wp, const float* bias, const float* gate, int64_t N,
+                            int64_t H, int64_t W, int cin, int cout, uint16_t* y, uint8_t* idx, hipStream_t stream);
+int rt1_lava_conv_gated_dgrad(const uint16_t* dy, const uint8_t* idx, const uint16_t* wd, const float* gate, int64_t N,
+                              int64_t H, int64_t W, int cin, int cout, uint16_t* dx, hipStream_t stream);
+int rt1_lava_conv_gated_wgrad(const uint16_t* x, const uint16_t* dy, const uint8_t* idx, const float* gate, int64_t N,
+                              int64_t H, int64_t W, int cin, int cout, float* part, float* dbpart, float* dW,
+                              float* db, hipStream_t stream);
+int rt1_lava_conv_dgate(const uint16_t* dy, const uint16_t* y, const float* gate, int64_t N, int64_t H, int64_t W,
+                        int cin, int cout, float* dgate, hipStream_t stream);
+
+// lavapix.hip: the tail of PixelLangMSE's encoder, out fp32 [N, 256] = LayerNorm(relu(mean_p(y4) * gate)) from
+// y4 bf16 [N, P, 256]; mean fp32 [N, 256] and stat fp32 [N, 2] = (mu, rstd) are kept for the backward, which writes
+// dy4 bf16 [N, P, 256], dgate fp32 [N, 256] and dgamma / dbeta fp32 [256] (rows fp32 [N, 2, 256]: workspace)
+int rt1_lava_pixel_tail_supported(int channels);
+int rt1_lava_pixel_tail_fwd(const uint16_t* y4, const float* gate, const float* lnw, const float* lnb, float eps,
+                            int64_t N, int64_t P, float* out, float* mean, float* stat, hipStream_t stream);
+int rt1_lava_pixel_tail_bwd(const float* dout, const float* mean, const float* stat, const float* gate,
+                            const float* lnw, int64_t N, int64_t P, uint16_t* dy4, float* dgate, float* rows,
+                            float* dgamma, float* dbeta, hipStream_t stream);
 
 // lavasent.hip: the LAVA visual sentence, pixels fp32 [N, S, 128] = drop((A_l W_l^T + b_l) sqrt(128) + pos) over fuse
 // levels (2, 3, 4): L2 bf16 [N, h2, w2, 128], L3 bf16 [N, h3, w3, 256], level 4 = the VALID 2x2 maxpool of L3 formed

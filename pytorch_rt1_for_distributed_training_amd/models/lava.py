@@ -357,11 +357,16 @@ class LanguageFusion(nn.Module):
 
 class ConvMaxpoolLanguageEncoder(nn.Module):
     """4 x [conv3x3 SAME (+bias) -> language fusion from the 2nd conv on -> ReLU -> maxpool 2 VALID], spatial
-    mean, a final multiplicative language gate, ReLU, LayerNorm (``pixel.py:47-80``, ``fuse_from = 2``)."""
+    mean, a final multiplicative language gate, ReLU, LayerNorm (``pixel.py:47-80``, ``fuse_from = 2``).
+
+    ``backend`` ``hip`` (``ops/lava_pixel.py``) runs the convs, gates, ReLUs, pools and the tail on HIP kernels; the
+    gate projections stay ``nn.Linear``.  It serves ``fuse_from == 2``, channels (32, 64, 128, 256) and 3, 6, 9 or 12
+    stacked input channels; the parameters are the same on both backends."""
 
     def __init__(self, in_ch: int, lang_dim: int = 512, channels: Sequence[int] = (32, 64, 128, 256),
-                 fuse_from: int = 2):
+                 fuse_from: int = 2, backend: str = "torch"):
         super().__init__()
+        self.backend = self._resolve(backend, in_ch, tuple(channels), fuse_from)
         convs, fuses, cin = [], [], in_ch
         for i, c in enumerate(channels):
             convs.append(_flax_conv(cin, c, 3))
@@ -373,7 +378,37 @@ class ConvMaxpoolLanguageEncoder(nn.Module):
         self.lang_gate = _dense(lang_dim, channels[-1]) if fuse_from <= len(channels) + 1 else None
         self.norm = nn.LayerNorm(channels[-1], eps=1e-6)
 
-    def forward(self, x, lang):                                          # x (B, C, H, W)
+    @staticmethod
+    def _resolve(backend: str, in_ch: int, channels, fuse_from: int) -> str:
+        if backend == "torch":
+            return "torch"
+        from ..ops.lava_conv import FIRST_STAGE_CIN
+        from ..ops.lava_pixel import CHANNELS, resolve_backend
+        missing = None
+        if fuse_from != 2:
+            missing = f"the hip pixel encoder serves fuse_from == 2, got {fuse_from}"
+        elif channels != CHANNELS:
+            missing = f"the hip pixel encoder serves channels {CHANNELS}, got {channels}"
+        elif in_ch not in FIRST_STAGE_CIN:
+            missing = (f"the hip pixel encoder is served for 3 * sequence_length in {FIRST_STAGE_CIN} stacked "
+                       f"channels, got {in_ch}")
+        if missing is None:
+            return resolve_backend(backend, in_ch, channels)             # ValueError when hip cannot be served
+        if backend == "auto":
+            return "torch"
+        resolve_backend(backend)                                         # an unknown name or a missing GPU comes first
+        raise ValueError(missing)
+
+    def forward(self, x, lang):            # torch: x (B, C, H, W); hip: the stacked frames (B, H, W, C), uint8 or fp32
+        if self.backend == "hip":
+            # per stage one MFMA kernel: conv + bias, the language gate, ReLU and pool in its epilogue, NHWC bf16
+            # between the stages (lavaconv.hip); mean, final gate, ReLU and LayerNorm in one launch (lavapix.hip)
+            from ..ops.lava_conv import conv_relu_pool, gated_conv_relu_pool
+            from ..ops.lava_pixel import pixel_tail
+            x = conv_relu_pool(x, self.convs[0])
+            for conv, fuse in zip(self.convs[1:], self.fuses[1:]):
+                x = gated_conv_relu_pool(x, conv, fuse.proj(lang))
+            return pixel_tail(x, self.lang_gate(lang), self.norm)
         for conv, fuse, on in zip(self.convs, self.fuses, self._fuse):
             x = conv(x)
             if on:
@@ -394,20 +429,25 @@ class PixelLangMSE(nn.Module):
     the encoder, then the dense resnet and an N(0, 0.05)-initialised action projection (``pixel.py:84-111``)."""
 
     def __init__(self, action_size: int = 2, dense_resnet_width: int = 1024, dense_resnet_num_blocks: int = 2,
-                 sequence_length: int = 4, lang_dim: int = 512, head_backend: str = "torch"):
+                 sequence_length: int = 4, lang_dim: int = 512, head_backend: str = "torch",
+                 encoder_backend: str = "torch"):
         super().__init__()
-        self.encoder = ConvMaxpoolLanguageEncoder(3 * sequence_length, lang_dim)
+        self.encoder = ConvMaxpoolLanguageEncoder(3 * sequence_length, lang_dim, backend=encoder_backend)
         self.dense_resnet = DenseResnet(256, dense_resnet_width, dense_resnet_num_blocks)
         self.action_projection = _dense(dense_resnet_width, action_size)
         self.dense_resnet.backend = _resolve_head(head_backend, self.dense_resnet, self.action_projection)
 
     def forward(self, obs) -> torch.Tensor:
         rgb = obs["rgb"]
+        hip = self.encoder.backend == "hip"                              # the kernels read NHWC and fuse the /255
         if rgb.dtype == torch.uint8:
-            rgb = rgb.float() / 255.0
+            if not hip:
+                rgb = rgb.float() / 255.0
+        elif hip:
+            rgb = rgb.float()
         b, n, w, h, c = rgb.shape
         rgb = rgb.contiguous().reshape(b, w, h, c * n)                  # reference's channel stacking
         lang = obs.get("clip_embedding", obs.get("instruction_embedding"))[:, -1]
         dtype = next(self.encoder.parameters()).dtype                    # fp32; fp64 in a .double() copy
-        x = self.encoder(rgb.permute(0, 3, 1, 2), lang.to(dtype))
+        x = self.encoder(rgb if hip else rgb.permute(0, 3, 1, 2), lang.to(dtype))
         return policy_head(x, self.dense_resnet, self.action_projection)

@@ -45,8 +45,8 @@ def main(argv=None):
     ap.add_argument("--backend", choices=["torch", "hip", "auto"], default="torch",
                     help="pixel-language cross attention: eager torch, the folded HIP kernels, or hip when available")
     ap.add_argument("--encoder_backend", choices=["torch", "hip", "auto"], default="torch",
-                    help="conv-maxpool image encoder: eager torch, the fused conv+ReLU+pool HIP kernels, or hip when "
-                         "available")
+                    help="conv-maxpool image encoder (for --network pixel the language-gated one and its tail): eager "
+                         "torch, the fused conv+ReLU+pool HIP kernels, or hip when available")
     ap.add_argument("--sentence_backend", choices=["torch", "hip", "auto"], default="torch",
                     help="level projections into the visual sentence: eager torch, the fused MFMA HIP kernels (needs "
                          "--encoder_backend hip), or hip when available")
@@ -92,7 +92,8 @@ def main(argv=None):
         augment = BCAugment(seed=a.seed + ctx.rank)
     if a.network == "pixel":
         from pytorch_rt1_for_distributed_training_amd.models.lava import PixelLangMSE
-        net = PixelLangMSE(sequence_length=a.sequence_length, head_backend=a.head_backend)
+        net = PixelLangMSE(sequence_length=a.sequence_length, head_backend=a.head_backend,
+                           encoder_backend=a.encoder_backend)
     else:
         net = SequenceLAVMSE(cfg)
     pre = []
